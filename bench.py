@@ -10,6 +10,13 @@ batching scheduler, paged KV cache, HIP-graph decode, on-device sampling with th
 default temperature=1.0 / top_p=0.95 / top_k=50). Weak scaling: the global batch is
 ``--batch-per-gpu * N``. ``value`` = total generated tokens / wall time over all ranks (max).
 
+A plain run builds the engine, warms up, times ``--steps`` steps of the headline config and prints one JSON line
+(``ms_per_step`` = milliseconds per timed step). ``--dump-outputs DIR`` also writes the last timed step's generated
+token ids (and its prompts) as ``DIR/*.npy``: prompts, weights and per-request sampling seeds are fixed by the
+arguments, so two builds can be compared token for token. ``--full`` adds everything else the benchmark measures: the
+second headline config (``--secondary``, GPT-2-XL engine-direct and served over gRPC, ``"secondary"`` in the JSON
+line) and, on N > 1 GPUs, the all-reduce latency probe (``"comm_probe"``).
+
 Launch: ``python bench.py`` (N=1), ``python bench.py --gpus N`` (this process becomes a GPU-free
 launcher: it starts N rank processes of itself with RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set,
 forwards rank 0's JSON line, and on any rank failure or the ``--timeout`` kills the others and exits
@@ -51,9 +58,16 @@ def main():
                     help="paged KV cache storage: bf16, or fp8 e4m3 rows with per-row scales")
     ap.add_argument("--greedy", action="store_true")
     ap.add_argument("--no-graphs", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the second headline model (--secondary, "
+                         "engine-direct and served over gRPC) and, with N > 1 GPUs, the all-reduce latency probe")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what the last timed step of the headline config returned to its "
+                         "caller as DIR/<name>.npy (float32): output_tokens [requests, gen_len] in request order, and "
+                         "prompt_tokens [requests, prompt_len], the prompts they continue")
     ap.add_argument("--secondary", default="gpt2-xl",
-                    help="second headline model timed after the first (TP=1 per GPU, data-parallel over N GPUs); "
-                         "'' or 'none' to skip")
+                    help="with --full: second headline model timed after the first (TP=1 per GPU, data-parallel over N "
+                         "GPUs); '' or 'none' to skip")
     ap.add_argument("--simulate-tp", type=int, default=0,
                     help="dev tool: one process computes rank 0 of a TP=N shard plan with no communication "
                          "(per-rank compute time at TP=N shapes; not a headline number)")
@@ -81,8 +95,9 @@ def main():
     # the gRPC clients run in their own process, started before this one touches the GPU (no fork of a
     # GPU-initialised process); they learn the server port on stdin once the engine is up
     client = None
-    if args.secondary not in ("", "none") and args.secondary != args.model and args.simulate_tp <= 1 \
-            and args.secondary_serve == "grpc":
+    secondary = args.full and args.secondary not in ("", "none") and args.secondary != args.model \
+        and args.simulate_tp <= 1
+    if secondary and args.secondary_serve == "grpc":
         from llmss_amd.models.config import get_preset
 
         nc = max(1, min(args.clients, args.batch_per_gpu))
@@ -113,16 +128,17 @@ def main():
         if rank == 0:
             print(f"[bench] {msg}", file=sys.stderr, flush=True)
 
-    if world > 1 and args.simulate_tp <= 1 and torch.cuda.is_available() and tp.comm is not None:
+    if args.full and world > 1 and args.simulate_tp <= 1 and torch.cuda.is_available() and tp.comm is not None:
         comm = comm_probe(tp, progress)
     else:
         comm = None
-    res = run_config(args, args.model, tp, args.batch_per_gpu * max(world, args.simulate_tp), progress)
+    res = run_config(args, args.model, tp, args.batch_per_gpu * max(world, args.simulate_tp), progress,
+                     dump=args.dump_outputs if rank == 0 else "")
     if comm is not None:
         res["comm_probe"] = comm
     if RCCL_TUNE_INFO:
         res["rccl_setting_probe"] = dict(RCCL_TUNE_INFO)
-    if args.secondary not in ("", "none") and args.simulate_tp <= 1 and args.secondary != args.model:
+    if secondary:
         # second BASELINE headline config (GPT-2-XL TP=1, 25 heads: no TP split), driver-timed in the same run;
         # with N GPUs every rank serves its own TP=1 replica (data parallel) and the node total is reported
         if torch.cuda.is_available():
@@ -355,9 +371,25 @@ def run_served(args, eng, client, progress, world, rank_sync):
     return el, sum(r["tokens"] for r in reps), reps
 
 
-def run_config(args, model_name, tp, batch, progress, dp=False, client=None):
+def dump_outputs(path, reqs):
+    """The last timed step's requests in submission order: what ``eng.generate`` would have returned for them
+    (token ids are exact in float32)."""
+    os.makedirs(path, exist_ok=True)
+    reqs = sorted(reqs, key=lambda r: r.id)
+    cap = (24 << 20) // (4 * max(len(r.prompt_ids) + len(r.output_ids) for r in reqs))  # rows; both files < 64 MB
+    if len(reqs) > cap:  # a fixed, seeded sample of the rows
+        reqs = [reqs[i] for i in sorted(np.random.default_rng(0).choice(len(reqs), cap, replace=False))]
+    for name, rows in (("output_tokens", [r.output_ids for r in reqs]), ("prompt_tokens", [r.prompt_ids for r in reqs])):
+        width = max(len(r) for r in rows)
+        arr = np.full((len(rows), width), -1.0, dtype=np.float32)  # -1 pads a request that ended early
+        for i, r in enumerate(rows):
+            arr[i, :len(r)] = r
+        np.save(os.path.join(path, name + ".npy"), arr)
+
+
+def run_config(args, model_name, tp, batch, progress, dp=False, client=None, dump=""):
     """Build ``model_name`` on ``tp`` (``dp``: an independent TP=1 replica per rank), warm up, time
-    ``args.steps`` batched generations; returns the JSON dict."""
+    ``args.steps`` batched generations; returns the JSON dict. ``dump``: directory for ``dump_outputs``."""
     from llmss_amd.engine import LLMEngine, SamplingParams, build_model
 
     world = args.gpus
@@ -389,6 +421,7 @@ def run_config(args, model_name, tp, batch, progress, dp=False, client=None):
     fault = tuple(fault.split(":")) if fault else None
     my_rank = tp.global_rank if tp.is_real else int(os.environ.get("RANK", "0"))
     steps_done = [0]
+    last_reqs = []  # the requests of the latest step, as the engine handed them back
 
     def one_step():
         if fault is not None and int(fault[0]) == my_rank and int(fault[1]) == steps_done[0]:
@@ -404,8 +437,8 @@ def run_config(args, model_name, tp, batch, progress, dp=False, client=None):
         n = 0
         while eng.has_unfinished():
             n += len(eng.step())
-        reqs = eng.pop_finished()
-        return n, [r.metrics() for r in reqs]
+        last_reqs[:] = eng.pop_finished()
+        return n, [r.metrics() for r in last_reqs]
 
     def sync():
         if dev.type == "cuda":
@@ -438,6 +471,9 @@ def run_config(args, model_name, tp, batch, progress, dp=False, client=None):
     sync()
     barrier()
     el = time.perf_counter() - t0
+    if dump and last_reqs:
+        dump_outputs(dump, last_reqs)
+        progress(f"wrote the last step's {len(last_reqs)} requests to {dump}")
     rank_el = [el]
     rt = [runtime_record(tp, eng, dp)]
     if world > 1 and args.simulate_tp <= 1:

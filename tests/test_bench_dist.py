@@ -27,7 +27,7 @@ def test_bench_two_ranks_gloo(n):
     """n = 8: the driver's full-node invocation rehearsed rank for rank (TP=8 over 8 gloo processes, a 16-head tiny
     Llama: 2 heads per rank)."""
     port = _free_port()
-    args = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--model",
+    args = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", str(n), "--model",
             "tiny-llama" if n <= 4 else "tiny-llama16h", "--secondary",
             "tiny-gpt2", "--steps", "2", "--warmup", "1", "--batch-per-gpu", "2", "--prompt-len", "8", "--gen-len", "4"]
     procs = []
@@ -79,6 +79,35 @@ def test_bench_self_launches_ranks():
     assert d["n_gpus"] == 2 and d["config"]["parallelism"] == "tp2" and d["rccl_world_size"] == 2
     assert len(d["rank_elapsed_s"]) == 2 and max(d["rank_elapsed_s"]) * 1e3 / 2 == pytest.approx(d["ms_per_step"],
                                                                                                  rel=1e-2)
+
+
+def test_bench_plain_run_is_lean_and_dumps_repeatable_outputs(tmp_path):
+    """Without --full only the headline config runs (no "secondary" even when one is named), --steps sets the number
+    of timed steps, and --dump-outputs writes the last step's tokens: float32, one row per request, the same from run
+    to run."""
+    import numpy as np
+
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"dump{i}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                            "--model", "tiny-llama", "--secondary", "tiny-gpt2", "--batch-per-gpu", "3", "--prompt-len",
+                            "8", "--gen-len", "4", "--dump-outputs", str(d)],
+                           env=_cpu_env(), capture_output=True, text=True, timeout=300, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        res = json.loads(lines[0])
+        assert "secondary" not in res and "comm_probe" not in res
+        assert res["steps"] == 3 and r.stderr.count("[bench] step ") == 3
+        assert abs(res["value"] * res["ms_per_step"] / 1e3 - 3 * 4) < 0.05  # requests x tokens per step
+        assert sorted(os.listdir(d)) == ["output_tokens.npy", "prompt_tokens.npy"]
+        dumps.append({n: np.load(d / f"{n}.npy") for n in ("output_tokens", "prompt_tokens")})
+    a, b = dumps
+    assert a["output_tokens"].dtype == np.float32 and a["output_tokens"].shape == (3, 4)
+    assert a["prompt_tokens"].shape == (3, 8) and (a["output_tokens"] >= 0).all()
+    for n in a:
+        assert np.array_equal(a[n], b[n]), n
 
 
 @pytest.mark.parametrize("kind", ["exit", "raise", "hang"])

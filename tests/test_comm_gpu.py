@@ -4,7 +4,7 @@ RCCL refuses two ranks on one GPU ("Duplicate GPU detected"), so these tests run
 communicator: they check the binding (dtype codes, pointers, streams), that the calls are captured into
 HIP graphs and replay, and the TP engine end to end with the native data plane in its graphs. They are
 capture smoke tests - a one-rank all-reduce moves no data. The multi-rank behaviour (sums over xGMI,
-per-collective latency) is measured by bench.py's comm probe in the driver's multi-GPU run
+per-collective latency) is measured by the comm probe of bench.py --full in the driver's multi-GPU run
 (``comm_probe`` in the bench JSON) and rehearsed on CPU by tests/test_bench_dist.py.
 """
 import pytest

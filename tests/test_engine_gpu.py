@@ -166,7 +166,7 @@ def test_rccl_collectives_inside_decode_graphs():
     all-reduces + all-gather through torch's RCCL process group captures into HIP graphs and replays ==
     eager. The communicator has ONE member, so its in-place all-reduces move no data and need not leave a
     node in the graph: this proves capture works, not that a multi-rank collective is in the graph (that is
-    measured by bench.py's comm probe on the driver's multi-GPU node)."""
+    measured by the comm probe of bench.py --full on the driver's multi-GPU node)."""
     import os
 
     import torch.distributed as dist
