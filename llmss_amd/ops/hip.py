@@ -347,6 +347,8 @@ def attn_decode(q, k_cache, v_cache, block_tables, ctx_lens, nh, nkv, D, scale, 
     nsplit, psize = splits if splits is not None else decode_splits(B, nkv, max_ctx, bs)
     _check(nsplit * psize >= max_ctx, "splits do not cover max_ctx")
     y = out if out is not None else torch.empty(B, nh * D, dtype=q.dtype, device=q.device)
+    _bf16_rows(y, "out")
+    _check(y.shape[0] >= B and y.shape[1] >= nh * D, "out shape")
     po, pml = _DECODE_WS.get(B, nh, nsplit, D, q.device) if nsplit > 1 else (None, None)
     lib().attn_decode(q.data_ptr(), q.stride(0), k_cache.data_ptr(), v_cache.data_ptr(), block_tables.data_ptr(),
                       block_tables.stride(0), ctx_lens.data_ptr(), y.data_ptr(), y.stride(0), _ptr(po), _ptr(pml),
