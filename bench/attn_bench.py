@@ -1,6 +1,9 @@
 """Decode-attention micro-benchmark: paged KV read bandwidth per configuration.
 
-usage: python bench/attn_bench.py [--B 64] [--ctx 192,1024] [--heads 32:32,32:8] [--bs 16]
+usage: python bench/attn_bench.py [--B 64] [--ctx 192,1024] [--heads 32:32,32:8] [--bs 16] [--window W] [--extend Q]
+
+--window W: sliding-window attention (each row reads its last W keys; bytes and TB/s count the keys read).
+--extend Q: time the extend kernel on a Q-row chunk per sequence instead of the decode kernel.
 """
 import argparse
 import os
@@ -25,6 +28,8 @@ def main():
     ap.add_argument("--rotate-mb", type=float, default=700,
                     help="K/V copies rotated over at least this many MB (default: past the 256 MiB Infinity Cache; "
                          "the decode step's own working set is ~20 GB)")
+    ap.add_argument("--window", type=int, default=0, help="sliding window in tokens (0 = full attention)")
+    ap.add_argument("--extend", type=int, default=0, help="rows per sequence through attn_extend (0 = decode kernel)")
     a = ap.parse_args()
     dev, bs, D = "cuda", a.bs, a.D
     for hk in a.heads.split(","):
@@ -32,8 +37,11 @@ def main():
         for ctx in map(int, a.ctx.split(",")):
             maxb = (ctx + bs - 1) // bs
             nb = a.B * maxb
-            kv_bytes = 2 * a.B * ctx * nkv * D * 2
-            ncopy = max(1, int(a.rotate_mb * 1e6 // kv_bytes) + 1)  # rotate copies past the 256 MiB Infinity Cache
+            keys = min(ctx, a.window + a.extend) if a.window else ctx  # keys a sequence reads
+            kv_bytes = 2 * a.B * keys * nkv * D * 2
+            alloc_bytes = 2 * a.B * ctx * nkv * D * 2
+            # rotate copies past the 256 MiB Infinity Cache (a long windowed context: few copies of a big cache)
+            ncopy = max(1, min(int(a.rotate_mb * 1e6 // kv_bytes) + 1, int(12e9 // alloc_bytes)))
             kcs = [torch.randn(nb, nkv, bs, D, device=dev).to(torch.bfloat16) for _ in range(ncopy)]
             vcs = [torch.randn_like(kcs[0]) for _ in range(ncopy)]
             pages = torch.randperm(nb, device=dev) if a.random_pages else torch.arange(nb, device=dev)
@@ -42,19 +50,33 @@ def main():
             q = torch.randn(a.B, (nh + 2 * nkv) * D, device=dev).to(torch.bfloat16)
             out = torch.empty(a.B, nh * D, device=dev, dtype=torch.bfloat16)
             res = {"B": a.B, "nh": nh, "nkv": nkv, "ctx": ctx, "MB": round(kv_bytes / 1e6, 1)}
+            if a.window:
+                res["window"] = a.window
+            if a.extend:
+                Q = a.extend
+                res["extend"] = Q
+                q = torch.randn(a.B * Q, (nh + 2 * nkv) * D, device=dev).to(torch.bfloat16)
+                out = torch.empty(a.B * Q, nh * D, device=dev, dtype=torch.bfloat16)
+                cu = (torch.arange(a.B + 1, device=dev) * Q).to(torch.int32)
             for u, sp in [(u, sp) for u in map(int, a.unrolls.split(",")) for sp in
                           (map(int, a.splits.split(",")) if a.splits else [0])]:
                 H.lib().attn_decode_set_unroll(u)
                 spl = None
                 if sp:
-                    ps = -(-ctx // sp)
+                    span = H.decode_span(ctx, bs, a.window)
+                    ps = -(-span // sp)
                     ps = -(-ps // bs) * bs
-                    spl = (-(-ctx // ps), ps)
+                    spl = (-(-span // ps), ps)
                 it = [0]
 
                 def f():
                     i = it[0] = (it[0] + 1) % ncopy
-                    H.attn_decode(q, kcs[i], vcs[i], bt, cl, nh, nkv, D, D ** -0.5, ctx, out=out, splits=spl)
+                    if a.extend:
+                        H.attn_extend(q, kcs[i], vcs[i], bt, cu, cl, a.extend, nh, nkv, D, D ** -0.5, out=out,
+                                      window=a.window)
+                    else:
+                        H.attn_decode(q, kcs[i], vcs[i], bt, cl, nh, nkv, D, D ** -0.5, ctx, out=out, splits=spl,
+                                      window=a.window)
                 for _ in range(5):
                     f()
                 torch.cuda.synchronize()

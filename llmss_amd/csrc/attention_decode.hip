@@ -44,12 +44,17 @@ __device__ __forceinline__ float token_sum(float s) {
 // KV8: the paged cache holds fp8 rows (D e4m3 bytes + fp32 scale at byte D, 16-B tail; reference.py
 // kv_rows_quant): each lane loads 8 bytes per token instead of 16 and the row scales multiply the score
 // (K) and the probability (V) instead of every element.
-template <int D, int GB, int UNROLL, bool PIPE = false, bool KV8 = false>
+// WIN: the row attends keys [lo, ctx) instead of [0, ctx), lo = max(kv_starts[b], ctx - window) (sliding-window
+// attention, and a cache whose first page was cut inside - PagedPast.truncate). The partitions are then laid
+// over the window: their origin is lo's page, so no split idles below the window and nothing below that page
+// is read from the block-table row (those entries belong to released pages and hold stale ids). A separate
+// instantiation: the unwindowed kernels keep their code, registers and occupancy.
+template <int D, int GB, int UNROLL, bool PIPE = false, bool KV8 = false, bool WIN = false>
 __global__ __launch_bounds__(256, GB == 1 ? 8 : 1) void attn_decode_kernel(
     const bf16_t* __restrict__ q, int64_t q_stride, void* __restrict__ kcv, void* __restrict__ vcv,
     const int* __restrict__ block_tables, int bt_stride, const int* __restrict__ ctx_lens, bf16_t* __restrict__ out,
     int64_t out_stride, float* __restrict__ part_o, float* __restrict__ part_ml, int nh, int nkv, int G, int ngroups,
-    int block_size, int part_size, float scale_log2) {
+    int block_size, int part_size, float scale_log2, int window, const int* __restrict__ kv_starts) {
   constexpr int LPT = D / 8;
   constexpr int TPW = 64 / LPT;
   constexpr int RB = KV8 ? D + 16 : D;  // cache row, in cache elements (bytes for fp8 rows)
@@ -87,13 +92,20 @@ __global__ __launch_bounds__(256, GB == 1 ? 8 : 1) void attn_decode_kernel(
   }
 
   const int ctx = min(ctx_lens[b], bt_stride * block_size);  // never index past the block table
-  const int start = split * part_size;
+  int lo = 0, origin = 0;
+  if constexpr (WIN) {
+    lo = min(max(max(kv_starts ? kv_starts[b] : 0, window > 0 ? ctx - window : 0), 0), ctx);  // lo == ctx: no key
+    origin = lo / block_size * block_size;
+  }
+  const int start = origin + split * part_size;
   const int end = min(ctx, start + part_size);
+  // first key of this partition; a partition without a key runs no loop and writes (m = -big, l = 0)
+  const int first = WIN ? max(start, lo) : start;
   const int* bt = block_tables + (int64_t)b * bt_stride;
   const int64_t head_off = (int64_t)kvh * block_size * RB + sub * 8;
   const int64_t page_stride = (int64_t)nkv * block_size * RB;
   constexpr int STEP = 4 * TPW;  // tokens per workgroup-iteration
-  const int lend = end;
+  const int lend = (!WIN || first < end) ? end : start;
 
   // page ids of this workgroup's context range, staged once in LDS: the token loop then needs no
   // dependent block-table load (an L2 round trip) in front of every K/V load. The staged range is the
@@ -124,7 +136,8 @@ __global__ __launch_bounds__(256, GB == 1 ? 8 : 1) void attn_decode_kernel(
 #pragma unroll
     for (int u = 0; u < UNROLL; ++u) {
       const int t = tb + u * STEP;
-      const int64_t a = kv_addr(t < lend ? t : start);
+      // an out-of-range token re-reads the partition's first key (never one below lo)
+      const int64_t a = kv_addr(WIN ? ((t < lend && t >= lo) ? t : first) : (t < lend ? t : start));
       // read once per step: non-temporal (guide 'nt-weights'; +10-15% on streamed reads)
       if constexpr (KV8) {
         r.k8[u] = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(kc8 + a));
@@ -140,7 +153,7 @@ __global__ __launch_bounds__(256, GB == 1 ? 8 : 1) void attn_decode_kernel(
   auto consume = [&](int tb, const KVRegs& r) {
 #pragma unroll
     for (int u = 0; u < UNROLL; ++u) {
-      const bool ok = tb + u * STEP < lend;
+      const bool ok = tb + u * STEP < lend && (!WIN || tb + u * STEP >= lo);
       float kf[8], vf[8], ks = 1.f, vs = 1.f;
       if constexpr (KV8) {
         const f32x2 k0 = __builtin_amdgcn_cvt_pk_f32_fp8(r.k8[u][0], false), k1 = __builtin_amdgcn_cvt_pk_f32_fp8(r.k8[u][0], true);
@@ -280,15 +293,24 @@ void attn_decode_set_unroll(int u) { g_decode_unroll = (u == 1 || u == 2 || u ==
 template <int D, int GB>
 static void launch_decode_t(const bf16_t* q, int64_t qs, bf16_t* kc, bf16_t* vc, const int* bt, int bts,
                             const int* cl, bf16_t* out, int64_t os, float* po, float* pml, int B, int nh, int nkv,
-                            int bs, int nsplit, int psize, float scale, hipStream_t st, bool kv8) {
+                            int bs, int nsplit, int psize, float scale, hipStream_t st, bool kv8, int window,
+                            const int* kvs) {
   const int G = nh / nkv;
   const int ngroups = (G + GB - 1) / GB;
   dim3 grid(B, nkv * ngroups, nsplit);
   const float sl2 = scale * kLog2e;
 #define AD(U_, PIPE_, KV8_)                                                                                      \
   attn_decode_kernel<D, GB, U_, PIPE_, KV8_><<<grid, 256, 0, st>>>(q, qs, kc, vc, bt, bts, cl, out, os, po, pml, nh, \
-                                                                  nkv, G, ngroups, bs, psize, sl2)
-  if (kv8) {
+                                                                  nkv, G, ngroups, bs, psize, sl2, 0, nullptr)
+  if (window > 0 || kvs != nullptr) {
+    // the windowed kernels exist for the default unroll only (the tuning knob covers the unwindowed ones)
+    if (kv8)
+      attn_decode_kernel<D, GB, 1, true, true, true><<<grid, 256, 0, st>>>(q, qs, kc, vc, bt, bts, cl, out, os, po, pml,
+                                                                           nh, nkv, G, ngroups, bs, psize, sl2, window, kvs);
+    else
+      attn_decode_kernel<D, GB, 1, true, false, true><<<grid, 256, 0, st>>>(q, qs, kc, vc, bt, bts, cl, out, os, po, pml,
+                                                                            nh, nkv, G, ngroups, bs, psize, sl2, window, kvs);
+  } else if (kv8) {
     switch (g_decode_unroll) {
       case 2: AD(2, false, true); break;
       case 12: AD(2, true, true); break;
@@ -315,21 +337,25 @@ static void launch_decode_t(const bf16_t* q, int64_t qs, bf16_t* kc, bf16_t* vc,
 template <int D>
 static void launch_decode_d(const bf16_t* q, int64_t qs, bf16_t* kc, bf16_t* vc, const int* bt, int bts,
                             const int* cl, bf16_t* out, int64_t os, float* po, float* pml, int B, int nh, int nkv,
-                            int bs, int nsplit, int psize, float scale, hipStream_t st, bool kv8) {
+                            int bs, int nsplit, int psize, float scale, hipStream_t st, bool kv8, int window,
+                            const int* kvs) {
   const int G = nh / nkv;
-  if (G == 1) launch_decode_t<D, 1>(q, qs, kc, vc, bt, bts, cl, out, os, po, pml, B, nh, nkv, bs, nsplit, psize, scale, st, kv8);
-  else if (G == 2) launch_decode_t<D, 2>(q, qs, kc, vc, bt, bts, cl, out, os, po, pml, B, nh, nkv, bs, nsplit, psize, scale, st, kv8);
-  else if (G <= 4) launch_decode_t<D, 4>(q, qs, kc, vc, bt, bts, cl, out, os, po, pml, B, nh, nkv, bs, nsplit, psize, scale, st, kv8);
-  else launch_decode_t<D, 8>(q, qs, kc, vc, bt, bts, cl, out, os, po, pml, B, nh, nkv, bs, nsplit, psize, scale, st, kv8);
+  if (G == 1) launch_decode_t<D, 1>(q, qs, kc, vc, bt, bts, cl, out, os, po, pml, B, nh, nkv, bs, nsplit, psize, scale, st, kv8, window, kvs);
+  else if (G == 2) launch_decode_t<D, 2>(q, qs, kc, vc, bt, bts, cl, out, os, po, pml, B, nh, nkv, bs, nsplit, psize, scale, st, kv8, window, kvs);
+  else if (G <= 4) launch_decode_t<D, 4>(q, qs, kc, vc, bt, bts, cl, out, os, po, pml, B, nh, nkv, bs, nsplit, psize, scale, st, kv8, window, kvs);
+  else launch_decode_t<D, 8>(q, qs, kc, vc, bt, bts, cl, out, os, po, pml, B, nh, nkv, bs, nsplit, psize, scale, st, kv8, window, kvs);
 }
 
 static void attn_decode_dispatch(const void* q, int64_t q_stride, void* kc, void* vc, const void* block_tables,
                                  int bt_stride, const void* ctx_lens, void* out, int64_t out_stride, void* part_o,
                                  void* part_ml, int B, int nh, int nkv, int D, int block_size, int nsplit,
-                                 int part_size, float scale, hipStream_t st, bool kv8 = false) {
+                                 int part_size, float scale, hipStream_t st, bool kv8, int window,
+                                 const void* kv_starts) {
   if (nh % nkv) throw std::runtime_error("attn_decode: nh must be a multiple of nkv");
   if (nsplit > 1 && (!part_o || !part_ml)) throw std::runtime_error("attn_decode: split needs workspaces");
+  if (window < 0) throw std::runtime_error("attn_decode: window must be >= 0");
   if (B == 0) return;
+  auto KVS = (const int*)kv_starts;
   auto Q = (const bf16_t*)q;
   auto K = (bf16_t*)kc;
   auto V = (bf16_t*)vc;
@@ -339,9 +365,9 @@ static void attn_decode_dispatch(const void* q, int64_t q_stride, void* kc, void
   auto PO = (float*)part_o;
   auto PML = (float*)part_ml;
   switch (D) {
-    case 64: launch_decode_d<64>(Q, q_stride, K, V, BT, bt_stride, CL, O, out_stride, PO, PML, B, nh, nkv, block_size, nsplit, part_size, scale, st, kv8); break;
-    case 128: launch_decode_d<128>(Q, q_stride, K, V, BT, bt_stride, CL, O, out_stride, PO, PML, B, nh, nkv, block_size, nsplit, part_size, scale, st, kv8); break;
-    case 256: launch_decode_d<256>(Q, q_stride, K, V, BT, bt_stride, CL, O, out_stride, PO, PML, B, nh, nkv, block_size, nsplit, part_size, scale, st, kv8); break;
+    case 64: launch_decode_d<64>(Q, q_stride, K, V, BT, bt_stride, CL, O, out_stride, PO, PML, B, nh, nkv, block_size, nsplit, part_size, scale, st, kv8, window, KVS); break;
+    case 128: launch_decode_d<128>(Q, q_stride, K, V, BT, bt_stride, CL, O, out_stride, PO, PML, B, nh, nkv, block_size, nsplit, part_size, scale, st, kv8, window, KVS); break;
+    case 256: launch_decode_d<256>(Q, q_stride, K, V, BT, bt_stride, CL, O, out_stride, PO, PML, B, nh, nkv, block_size, nsplit, part_size, scale, st, kv8, window, KVS); break;
     default: throw std::runtime_error("attn_decode: head_dim must be 64, 128 or 256");
   }
 }
@@ -349,8 +375,8 @@ static void attn_decode_dispatch(const void* q, int64_t q_stride, void* kc, void
 void launch_attn_decode(const void* q, int64_t q_stride, const void* kc, const void* vc, const void* block_tables,
                         int bt_stride, const void* ctx_lens, void* out, int64_t out_stride, void* part_o,
                         void* part_ml, int B, int nh, int nkv, int D, int block_size, int nsplit, int part_size,
-                        float scale, hipStream_t st, bool kv8) {
+                        float scale, hipStream_t st, bool kv8, int window, const void* kv_starts) {
   attn_decode_dispatch(q, q_stride, const_cast<void*>(kc), const_cast<void*>(vc), block_tables, bt_stride, ctx_lens,
                        out, out_stride, part_o, part_ml, B, nh, nkv, D, block_size, nsplit, part_size, scale, st,
-                       kv8);
+                       kv8, window, kv_starts);
 }

@@ -27,12 +27,16 @@ constexpr float kLog2eX = 1.4426950408889634f;
 // absmax / 448 scale and clamped conversion) for the W8A8 o-projection that consumes them, which then skips its own
 // quantisation launch. Only when a workgroup holds every head of its rows: one kv head (nkv = 1) whose whole query
 // group fits the slots of a wave (GE = G, a power of two <= 16) - Llama-2-70B at TP=8 (8 query heads per rank).
-template <int D, bool KV8>
+// WIN: the row at position p attends keys [max(kv_starts[b], p - window + 1), p] instead of [0, p] (sliding-window
+// attention; a cache whose first page was cut inside). A workgroup's tiles then start at its lowest row's first
+// key, and nothing below that key's page is read from the block-table row (released pages, stale ids). A separate
+// instantiation: the unwindowed kernels keep their code and registers.
+template <int D, bool KV8, bool WIN>
 __global__ __launch_bounds__(256) void attn_extend_kernel(
     const bf16_t* __restrict__ q, int64_t q_stride, const void* __restrict__ kcv, const void* __restrict__ vcv,
     const int* __restrict__ block_tables, int max_blocks, const int* __restrict__ cu_q, const int* __restrict__ ctx_lens,
     bf16_t* __restrict__ out, int64_t out_stride, int nh, int nkv, int GE, int bs, float scale_log2,
-    unsigned char* __restrict__ q8, float* __restrict__ s8) {
+    unsigned char* __restrict__ q8, float* __restrict__ s8, int window, const int* __restrict__ kv_starts) {
   constexpr int BKV = 64;
   constexpr int LD = D + 16;  // padded LDS row (elements): conflict-free b128 rows and tr_b16 columns
   __shared__ __attribute__((aligned(16))) bf16_t Ks[BKV * LD];
@@ -69,6 +73,13 @@ __global__ __launch_bounds__(256) void attn_extend_kernel(
   // keys needed by this workgroup: [0, last valid row's position]
   const int r_last = min(qlen, r0 + rows_per_wg) - 1;
   const int kv_end = p0 + r_last + 1;
+  // first key of a row at position p; the workgroup's tiles start at its lowest row's
+  const int kvs = WIN ? min(kv_starts ? kv_starts[b] : 0, kv_end) : 0;  // kvs == kv_end: no key
+  auto row_lo = [&](int p) { return WIN ? max(max(kvs, window > 0 ? p - window + 1 : 0), 0) : 0; };
+  const int kv_begin = row_lo(p0 + r0);
+  const int qlo = row_lo(qpos);
+  const int wave_lo = row_lo(p0 + min(qlen - 1, r0 + (16 * w) / GE));
+  const int pgb = kv_begin / bs;  // first staged page of the row
   // this wave's slots: rows r0 + (16w)/GE .. r0 + (16w+15)/GE
   const int wave_qhi = p0 + min(qlen - 1, r0 + (16 * w + 15) / GE);
   const int* bt = block_tables + (int64_t)b * max_blocks;
@@ -83,10 +94,10 @@ __global__ __launch_bounds__(256) void attn_extend_kernel(
   // block-table load (an L2 round trip per tile)
   constexpr int kMaxPages = 512;
   __shared__ int s_pages[kMaxPages];
-  const int npg = (kv_end + bs - 1) / bs;
+  const int npg = (kv_end + bs - 1) / bs - pgb;
   const bool lds_pages = npg <= kMaxPages;
   if (lds_pages)
-    for (int i = threadIdx.x; i < npg; i += 256) s_pages[i] = bt[i];
+    for (int i = threadIdx.x; i < npg; i += 256) s_pages[i] = bt[pgb + i];
   __syncthreads();
   // Software pipeline: tile t+1's K/V chunks are loaded into registers while tile t is computed from LDS
   // (the register set is written to LDS after the next barrier), so each tile no longer waits a full
@@ -102,7 +113,7 @@ __global__ __launch_bounds__(256) void attn_extend_kernel(
       const int c = threadIdx.x + j * 256;
       const int r = c / CH, ch = c % CH;
       const int key = min(kv0 + r, kv_end - 1);
-      const int blk = lds_pages ? s_pages[key / bs] : bt[key / bs];
+      const int blk = lds_pages ? s_pages[key / bs - pgb] : bt[key / bs];
       const int64_t rowoff = ((int64_t)blk * nkv + kvh) * head_stride + (int64_t)(key % bs) * RB;
       if constexpr (KV8) {
         kr8[j] = *reinterpret_cast<const u32x2*>(kc8 + rowoff + ch * 8);
@@ -146,7 +157,7 @@ __global__ __launch_bounds__(256) void attn_extend_kernel(
     for (int c = threadIdx.x; c < BKV * CH; c += 256) {
       const int r = c / CH, ch = c % CH;
       const int key = min(kv0 + r, kv_end - 1);
-      const int blk = lds_pages ? s_pages[key / bs] : bt[key / bs];
+      const int blk = lds_pages ? s_pages[key / bs - pgb] : bt[key / bs];
       const int64_t rowoff = ((int64_t)blk * nkv + kvh) * head_stride + (int64_t)(key % bs) * RB;
       if constexpr (KV8) {
         kr8[0] = *reinterpret_cast<const u32x2*>(kc8 + rowoff + ch * 8);
@@ -172,9 +183,9 @@ __global__ __launch_bounds__(256) void attn_extend_kernel(
     }
   };
   if constexpr (PIPE) {
-    if (kv_end > 0) load_tile(0);
+    if (kv_end > kv_begin) load_tile(kv_begin);
   }
-  for (int kv0 = 0; kv0 < kv_end; kv0 += BKV) {
+  for (int kv0 = kv_begin; kv0 < kv_end; kv0 += BKV) {
     __syncthreads();  // every wave is done reading the previous tile
     if constexpr (PIPE) store_tile();
     else stage_direct(kv0);
@@ -183,6 +194,9 @@ __global__ __launch_bounds__(256) void attn_extend_kernel(
       if (kv0 + BKV < kv_end) load_tile(kv0 + BKV);
     }
     if (kv0 > wave_qhi) continue;  // whole tile in this wave's causal future (barriers stay uniform)
+    if constexpr (WIN) {
+      if (kv0 + BKV <= wave_lo) continue;  // whole tile below the windows of this wave's slots
+    }
 
     f32x4 s[4];
 #pragma unroll
@@ -202,7 +216,7 @@ __global__ __launch_bounds__(256) void attn_extend_kernel(
       for (int i = 0; i < 4; ++i) {
         const int key = kv0 + kt * 16 + 4 * g + i;
         float v = s[kt][i] * scale_log2;
-        v = (key <= qpos && key < kv_end) ? v : -1.0e30f;
+        v = (key <= qpos && key < kv_end && (!WIN || key >= qlo)) ? v : -1.0e30f;
         s[kt][i] = v;
         mx = fmaxf(mx, v);
       }
@@ -216,7 +230,10 @@ __global__ __launch_bounds__(256) void attn_extend_kernel(
     for (int kt = 0; kt < 4; ++kt)
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        const float p = exp2f(s[kt][i] - mx);
+        float p = exp2f(s[kt][i] - mx);
+        // a slot may meet a tile of masked keys only before its first real key: then m == mx == -1e30 and
+        // exp2(0) would count every masked key (unwindowed, key 0 is always in the first tile)
+        if constexpr (WIN) p = s[kt][i] == -1.0e30f ? 0.f : p;
         const bf16_t pb = f2bf(p);
         ps += bf2f(pb);
         pf[kt >> 1][(kt & 1) * 4 + i] = (short)pb;
@@ -289,7 +306,8 @@ static int extend_group(int G) {
 void launch_attn_extend(const void* q, int64_t q_stride, const void* k_cache, const void* v_cache,
                         const void* block_tables, int max_blocks, const void* cu_q, const void* ctx_lens, void* out,
                         int64_t out_stride, int B, int max_qlen, int nh, int nkv, int D, int bs, float scale,
-                        hipStream_t st, bool kv8, void* q8v, void* s8v) {
+                        hipStream_t st, bool kv8, void* q8v, void* s8v, int window, const void* kv_starts) {
+  if (window < 0) throw std::runtime_error("attn_extend: window must be >= 0");
   if (nh % nkv) throw std::runtime_error("attn_extend: nh must be a multiple of nkv");
   if (B == 0 || max_qlen == 0) return;
   const int G = nh / nkv, GE = extend_group(G);
@@ -308,14 +326,20 @@ void launch_attn_extend(const void* q, int64_t q_stride, const void* k_cache, co
   auto CL = (const int*)ctx_lens;
   auto O = (bf16_t*)out;
   const float sl = scale * kLog2eX;
+  auto KVS = (const int*)kv_starts;
+  const bool win = window > 0 || KVS != nullptr;
+#define LXK(D_, KV8_, WIN_)                                                                                      \
+  attn_extend_kernel<D_, KV8_, WIN_><<<grid, 256, 0, st>>>(Q, q_stride, K, V, BT, max_blocks, CU, CL, O, out_stride,  \
+                                                           nh, nkv, GE, bs, sl, Q8, S8, window, KVS)
 #define LX(D_)                                                                                                   \
   do {                                                                                                           \
-    if (kv8)                                                                                                     \
-      attn_extend_kernel<D_, true><<<grid, 256, 0, st>>>(Q, q_stride, K, V, BT, max_blocks, CU, CL, O, out_stride, nh, \
-                                                         nkv, GE, bs, sl, Q8, S8);                               \
-    else                                                                                                         \
-      attn_extend_kernel<D_, false><<<grid, 256, 0, st>>>(Q, q_stride, K, V, BT, max_blocks, CU, CL, O, out_stride,   \
-                                                          nh, nkv, GE, bs, sl, Q8, S8);                          \
+    if (kv8) {                                                                                                   \
+      if (win) LXK(D_, true, true);                                                                              \
+      else LXK(D_, true, false);                                                                                 \
+    } else {                                                                                                     \
+      if (win) LXK(D_, false, true);                                                                             \
+      else LXK(D_, false, false);                                                                                \
+    }                                                                                                            \
   } while (0)
   switch (D) {
     case 64: LX(64); break;
@@ -324,5 +348,6 @@ void launch_attn_extend(const void* q, int64_t q_stride, const void* k_cache, co
     default: throw std::runtime_error("attn_extend: head_dim must be 64, 128 or 256");
   }
 #undef LX
+#undef LXK
   HIP_CHECK_LAUNCH();
 }

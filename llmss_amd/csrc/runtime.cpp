@@ -100,10 +100,11 @@ struct SeqState {
   int max_new;
   int num_tokens;    // prompt + generated tokens known
   int num_computed;  // tokens whose K/V are in the cache (scheduled into a step)
-  std::vector<int> blocks;
+  std::vector<int> blocks;  // logical length; entries [0, released) are -1 (sliding window: given back)
   int status;  // 0 waiting, 1 running, 2 finished
   int64_t order;
   int preemptions = 0;
+  int released = 0;  // leading blocks wholly below the attention window, returned to the allocator
 };
 
 struct StepBatch {
@@ -128,16 +129,32 @@ struct StepBatch {
 //      (prefill_chunk > 0 caps one chunk; prefill_chunk < 0 keeps prompts whole).
 // Decodes therefore never stall behind a long prompt (the prompt is cut into chunks that ride along
 // with the decode tokens), and a chunk's attention reads its own prefix from the paged cache.
+//
+// Sliding-window attention (window > 0): a query at position p reads keys (p - window, p] only, so
+//   * a prompt chunk is at most `window` tokens (the first chunk of a prompt then needs no lower mask);
+//   * before a step whose first query position is p0 is emitted, every block whose last position is below
+//     p0 - window + 1 goes back to the allocator (plan() and reserve()). SeqState.blocks keeps its logical
+//     length: released entries are -1 there and 0 in the step's block table, which the kernels never read
+//     below the window's first page;
+//   * admission checks the pool against the blocks a sequence can hold live, not its whole length.
+// Why a released block may be handed out again at once: every step that reads it was launched before the step
+// that will write it, and steps run in stream order - also under the two-micro-batch and comm-stream
+// schedules of models/decoder.py, whose side streams fork from and join back to the compute stream inside
+// one step (StreamLedger), so no kernel of an earlier step is still running when a later step's first kernel
+// starts. Release depends on (num_computed, window, block_size) alone, so every rank's scheduler copy
+// releases the same blocks at the same call.
 class Scheduler {
  public:
   Scheduler(int num_blocks, int block_size, int max_num_seqs, int max_batched_tokens, int max_model_len,
-            int prefill_chunk = 0)
+            int prefill_chunk = 0, int window = 0)
       : alloc_(num_blocks, block_size),
         bs_(block_size),
         max_seqs_(max_num_seqs),
         max_tokens_(max_batched_tokens),
         max_len_(max_model_len),
-        chunk_(prefill_chunk) {
+        chunk_(prefill_chunk),
+        window_(window) {
+    if (window < 0) throw std::invalid_argument("Scheduler: window must be >= 0");
     max_blocks_per_seq_ = (max_model_len + block_size - 1) / block_size;
     if (max_batched_tokens <= 0) throw std::invalid_argument("Scheduler: max_batched_tokens must be > 0");
   }
@@ -149,7 +166,9 @@ class Scheduler {
       throw std::invalid_argument("Scheduler.add: prompt_len + max_new_tokens exceeds max_model_len");
     if (chunk_ < 0 && prompt_len > max_tokens_)
       throw std::invalid_argument("Scheduler.add: prompt longer than max_batched_tokens (whole-prompt mode)");
-    if ((int64_t)blocks_for(prompt_len + max_new) > (int64_t)alloc_.num_blocks())
+    if (window_ > 0 && chunk_ < 0 && prompt_len > window_)
+      throw std::invalid_argument("Scheduler.add: prompt longer than the attention window (whole-prompt mode)");
+    if ((int64_t)live_bound(prompt_len, max_new) > (int64_t)alloc_.num_blocks())
       throw std::invalid_argument("Scheduler.add: sequence needs more KV blocks than the whole pool holds");
     SeqState s{id, prompt_len, max_new, prompt_len, 0, {}, 0, counter_++};
     seqs_.emplace(id, s);
@@ -177,8 +196,7 @@ class Scheduler {
     auto it = seqs_.find(id);
     if (it == seqs_.end()) return;
     auto& s = it->second;
-    alloc_.free_all(s.blocks);
-    s.blocks.clear();
+    free_live(s);
     if (s.status == 1) running_.erase(std::remove(running_.begin(), running_.end(), id), running_.end());
     if (s.status == 0) waiting_.erase(std::remove(waiting_.begin(), waiting_.end(), id), waiting_.end());
     seqs_.erase(it);
@@ -221,6 +239,7 @@ class Scheduler {
     for (size_t i = 0; i < order.size() && budget > 0; ++i) {
       auto& s = get(order[i]);
       if (s.status != 1 || s.num_tokens - s.num_computed != 1) continue;
+      release(s, s.num_computed);
       while ((int)s.blocks.size() * bs_ < s.num_tokens) {
         if (alloc_.can_allocate(1)) {
           s.blocks.push_back(alloc_.allocate());
@@ -249,6 +268,7 @@ class Scheduler {
       if (s.status != 1 || s.num_tokens - s.num_computed <= 1) continue;
       const int q = chunk_len(s, budget);
       if (q <= 0) break;
+      release(s, s.num_computed);
       if (!grow(s, s.num_computed + q)) {
         starved = true;
         break;
@@ -294,7 +314,9 @@ class Scheduler {
     auto it = seqs_.find(id);
     if (it == seqs_.end()) return -1;  // finished / aborted meanwhile: nothing to reserve for
     auto& s = it->second;
-    if (s.status != 1 || n_tokens <= 0 || blocks_for(n_tokens) > max_blocks_per_seq_ || !grow(s, n_tokens)) return -1;
+    if (s.status != 1 || n_tokens <= 0 || blocks_for(n_tokens) > max_blocks_per_seq_) return -1;
+    release(s, n_tokens - 1);  // the reserved step's query sits at position n_tokens - 1
+    if (!grow(s, n_tokens)) return -1;
     return s.blocks[(n_tokens - 1) / bs_];
   }
   int num_tokens(int64_t id) { return get(id).num_tokens; }
@@ -312,10 +334,37 @@ class Scheduler {
   int64_t slot(const SeqState& s, int p) const { return (int64_t)s.blocks[p / bs_] * bs_ + p % bs_; }
   int chunk_len(const SeqState& s, int budget) const {
     const int rem = s.num_tokens - s.num_computed;
-    if (chunk_ < 0) return rem <= budget ? rem : 0;  // whole prompts only
+    // whole prompts only (a preempted windowed sequence recomputing more than a window is chunked after all)
+    if (chunk_ < 0 && (window_ == 0 || rem <= window_)) return rem <= budget ? rem : 0;
     int q = std::min(rem, budget);
     if (chunk_ > 0) q = std::min(q, chunk_);
+    if (window_ > 0) q = std::min(q, window_);
     return q;
+  }
+  // Most blocks a sequence holds at once: all of them without a window; with one, the pages of the keys
+  // (p0 - window, p0 + q) of its longest step, plus one page of release lag (reserve() releases only when a
+  // sequence enters a new block).
+  int live_bound(int prompt_len, int max_new) const {
+    const int all = blocks_for(prompt_len + max_new);
+    if (window_ == 0) return all;
+    int q = std::min(prompt_len, window_);
+    if (chunk_ > 0) q = std::min(q, chunk_);
+    return std::min(all, blocks_for(window_ + q) + 2);
+  }
+  // Give back the blocks wholly below the window of a step whose first query position is p0.
+  void release(SeqState& s, int p0) {
+    if (window_ == 0) return;
+    const int n = std::min((int)s.blocks.size(), std::max(0, p0 - window_ + 1) / bs_);
+    for (int i = s.released; i < n; ++i) {
+      alloc_.free(s.blocks[i]);
+      s.blocks[i] = -1;
+    }
+    s.released = std::max(s.released, n);
+  }
+  void free_live(SeqState& s) {
+    for (size_t i = s.released; i < s.blocks.size(); ++i) alloc_.free(s.blocks[i]);
+    s.blocks.clear();
+    s.released = 0;
   }
   bool grow(SeqState& s, int n_tokens) {  // blocks for n_tokens cached tokens, no preemption
     const int need = blocks_for(n_tokens) - (int)s.blocks.size();
@@ -338,8 +387,7 @@ class Scheduler {
   }
   void preempt(int64_t id) {
     auto& s = get(id);
-    alloc_.free_all(s.blocks);
-    s.blocks.clear();
+    free_live(s);
     s.num_computed = 0;
     s.status = 0;
     s.preemptions++;
@@ -352,12 +400,14 @@ class Scheduler {
     b.block_table.assign((size_t)B * b.max_blocks, 0);
     for (int i = 0; i < B; ++i) {
       const auto& s = get(b.ids[i]);
-      std::copy(s.blocks.begin(), s.blocks.end(), b.block_table.begin() + (size_t)i * b.max_blocks);
+      // released entries stay 0 (a valid page id; the kernels read nothing below the window's first page)
+      std::copy(s.blocks.begin() + s.released, s.blocks.end(),
+                b.block_table.begin() + (size_t)i * b.max_blocks + s.released);
     }
   }
 
   BlockAllocator alloc_;
-  int bs_, max_seqs_, max_tokens_, max_len_, max_blocks_per_seq_, chunk_;
+  int bs_, max_seqs_, max_tokens_, max_len_, max_blocks_per_seq_, chunk_, window_;
   std::unordered_map<int64_t, SeqState> seqs_;
   std::deque<int64_t> waiting_;
   std::vector<int64_t> running_;
@@ -707,9 +757,9 @@ void register_runtime(py::module_& m) {
       .def_property_readonly("preempted", [](const StepBatch& b) { return to_np(b.preempted); });
 
   py::class_<Scheduler>(m, "Scheduler")
-      .def(py::init<int, int, int, int, int, int>(), py::arg("num_blocks"), py::arg("block_size"),
+      .def(py::init<int, int, int, int, int, int, int>(), py::arg("num_blocks"), py::arg("block_size"),
            py::arg("max_num_seqs"), py::arg("max_batched_tokens"), py::arg("max_model_len"),
-           py::arg("prefill_chunk") = 0)
+           py::arg("prefill_chunk") = 0, py::arg("window") = 0)
       .def("add", &Scheduler::add)
       .def("on_token", &Scheduler::on_token)
       .def("on_tokens",

@@ -167,8 +167,12 @@ class LLMEngine:
         # running decodes (prefill_chunk > 0 caps a chunk further; < 0 keeps prompts whole)
         self.prefill_chunk = int(prefill_chunk if prefill_chunk is not None else
                                  os.environ.get("LLMSS_PREFILL_CHUNK", "0"))
+        # sliding-window attention (Mistral): the scheduler caps prompt chunks at the window and gives blocks
+        # below it back to the pool; every paged attention call gets the window as a launch constant
+        self.window = int(self.cfg.sliding_window)
+        self.window = self.window if 0 < self.window < self.max_model_len else 0
         self.sched = _native().Scheduler(self.num_blocks, block_size, max_num_seqs, self.max_batched_tokens,
-                                         self.max_model_len, self.prefill_chunk)
+                                         self.max_model_len, self.prefill_chunk, self.window)
         self.requests: Dict[int, Request] = {}
         self._next_id = 0
         self._pending = collections.deque()  # launched GPU decode steps whose tokens are not yet processed
@@ -180,7 +184,7 @@ class LLMEngine:
         self.async_decode = os.environ.get("LLMSS_ASYNC_DECODE", "1") != "0"
         self.check_tokens = check_tokens if check_tokens is not None else os.environ.get("LLMSS_CHECK_TOKENS") == "1"
         self.stats = {"steps": 0, "prefill_steps": 0, "decode_steps": 0, "tokens": 0, "prefill_tokens": 0,
-                      "preemptions": 0, "decode_time_s": 0.0, "prefill_time_s": 0.0}
+                      "preemptions": 0, "decode_time_s": 0.0, "prefill_time_s": 0.0, "peak_live_kv_blocks": 0}
         self.timer = PhaseTimer()  # LLMSS_TIMING=1: HIP-event device time per phase; LLMSS_ROCTX=1: roctx ranges
         self._host_prof = self.timer.enabled  # LLMSS_TIMING=1 also records host-side time per engine phase
         self.use_graphs = self.is_gpu if use_graphs is None else (use_graphs and self.is_gpu)
@@ -259,7 +263,7 @@ class LLMEngine:
                 "num_blocks": self.num_blocks, "max_model_len": self.max_model_len,
                 "max_num_seqs": self.max_num_seqs, "max_batched_tokens": self.max_batched_tokens,
                 "buckets": list(self.buckets), "graphs": bool(self.use_graphs),
-                "async_decode": self.async_decode, "eos": self.eos, "prefill_chunk": self.prefill_chunk,
+                "async_decode": self.async_decode, "eos": self.eos, "prefill_chunk": self.prefill_chunk, "window": self.window,
                 "dist_sampling": self.dist_sampling, "kv_fp8": bool(self.model.kv_fp8),
                 "overlap_rows": self.model.overlap_rows, "bucket_bytes": self.model.bucket_bytes,
                 "tbo_min": self.model.tbo_min, "graph_keys": sorted(self.graphs),
@@ -328,10 +332,10 @@ class LLMEngine:
 
             def valu(i):
                 ops.attn_decode(qkv, kc, vc, bt, cl, p.nh_l, p.nkv_l, D, m.scale, self.max_model_len, splits=sp,
-                                out=out)
+                                out=out, window=self.window)
 
             def mfma(i):
-                ops.attn_extend(qkv, kc, vc, bt, cu, cl, 1, p.nh_l, p.nkv_l, D, m.scale, out=out)
+                ops.attn_extend(qkv, kc, vc, bt, cu, cl, 1, p.nh_l, p.nkv_l, D, m.scale, out=out, window=self.window)
             valu(0)
             mfma(0)
             torch.cuda.synchronize()
@@ -393,7 +397,13 @@ class LLMEngine:
             m.tbo_min = old
 
     def _splits(self, b):
-        return _hip_ops.decode_splits(b, self.model.plan.nkv_l, self.max_model_len, self.block_size)
+        span = _hip_ops.decode_span(self.max_model_len, self.block_size, self.window)
+        return _hip_ops.decode_splits(b, self.model.plan.nkv_l, span, self.block_size)
+
+    def _note_live_blocks(self):
+        live = self.num_blocks - self.sched.num_free_blocks()
+        if live > self.stats["peak_live_kv_blocks"]:
+            self.stats["peak_live_kv_blocks"] = live
 
     # -------------------------------------------------------------------------- requests
     def add_request(self, prompt_ids: Sequence[int], params: Optional[SamplingParams] = None,
@@ -470,6 +480,7 @@ class LLMEngine:
         t_b = time.perf_counter() if hp else 0.0
         with trace_range("schedule"):
             batch = self.sched.schedule()
+        self._note_live_blocks()
         if hp:
             t_c = time.perf_counter()
             self.stats["host_collect_apply_s"] = self.stats.get("host_collect_apply_s", 0.0) + t_b - t_a
@@ -573,7 +584,7 @@ class LLMEngine:
             max_seqlen=int(qlens[nd:].max()), last_idx=d((ends - 1)[smp]),
             block_tables=d(batch.block_table.astype(np.int32)) if kind == "extend" else None,
             ctx_lens=d(ctx.astype(np.int32)) if kind == "extend" else None, max_ctx=self.max_model_len,
-            num_decode=nd, has_prefix=has_prefix, cu_host=cu if kind == "prefill" else None)
+            num_decode=nd, has_prefix=has_prefix, cu_host=cu if kind == "prefill" else None, window=self.window)
         reqs = [r for r, f in zip(reqs, smp) if f]
         if not reqs:
             self.model.hidden_states(inp, self.kv)  # prompt chunks only: fill the cache, nothing to sample
@@ -605,7 +616,7 @@ class LLMEngine:
     def _decode_forward(self, b: int, buf: _DecodeBuffers, dist: bool = False):
         inp = StepInput(kind="decode", input_ids=buf.ids[:b], positions=buf.pos[:b], slots=buf.slots[:b],
                         block_tables=buf.bt[:b], ctx_lens=buf.ctx[:b], max_ctx=self.max_model_len,
-                        decode_splits=self._splits(b))
+                        decode_splits=self._splits(b), window=self.window)
         self._forward_sample(inp, buf.temp[:b], buf.topk[:b], buf.topp[:b], buf.seeds[:b], out=buf.out[:b],
                              dist=dist)
 
@@ -615,7 +626,8 @@ class LLMEngine:
         inp = StepInput(kind="decode", input_ids=torch.from_numpy(ids), positions=torch.from_numpy(batch.positions),
                         slots=torch.from_numpy(batch.slots),
                         block_tables=torch.from_numpy(batch.block_table.astype(np.int32)),
-                        ctx_lens=torch.from_numpy(batch.ctx_lens.astype(np.int32)), max_ctx=self.max_model_len)
+                        ctx_lens=torch.from_numpy(batch.ctx_lens.astype(np.int32)), max_ctx=self.max_model_len,
+                        window=self.window)
         return self._forward_sample(inp, temp, topk, topp, seeds, dist=self._dist_ok(temp, topk)).tolist()
 
     # ------------------------------------------------------------------ pipelined GPU decode
@@ -695,6 +707,7 @@ class LLMEngine:
                     return
                 bt[i, int(nxt_pos[i]) // bs] = blk
                 slots[i] = blk * bs
+            self._note_live_blocks()
             self.stats["spec_block_reserves"] = self.stats.get("spec_block_reserves", 0) + int(cross.size)
         dead = ~alive
         rec = {k: cur[k] for k in ("ids", "reqs", "n", "temp", "topk", "topp", "seed", "maxnew", "dist")}

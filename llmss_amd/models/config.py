@@ -14,7 +14,8 @@ Families (``MODEL_REGISTRY`` keys, reference ``custom_modeling/__init__.py:4-7``
                     separate q/k/v without bias, lm_head with bias (``gptj_modeling.py``).
 * ``gpt_bigcode`` - LayerNorm, learned positions, MQA (or MHA) fused c_attn, tied head
                     (``gpt_bigcode_modeling.py``).
-* ``llama``       - RMSNorm, half-rotate RoPE, GQA, SwiGLU, untied head.
+* ``llama``       - RMSNorm, half-rotate RoPE, GQA, SwiGLU, untied head. ``mistral`` checkpoints parse to this
+                    family plus ``sliding_window``.
 """
 from __future__ import annotations
 
@@ -53,6 +54,8 @@ class ModelConfig:
     bos_token_id: Optional[int] = None
     eos_token_id: Optional[int] = None
     pad_token_id: Optional[int] = None
+    # sliding-window attention (Mistral): a query at position p attends keys p - W < j <= p; 0 = full attention
+    sliding_window: int = 0
     extra: Dict[str, Any] = field(default_factory=dict)
 
     # ---------------------------------------------------------------- derived
@@ -132,16 +135,20 @@ class ModelConfig:
         if mt in ("llama", "mistral"):
             h, nh = d["hidden_size"], d["num_attention_heads"]
             hd = d.get("head_dim") or h // nh
+            max_pos = d.get("max_position_embeddings", 4096)
+            # a window that no position can exceed is full attention: such a config stays on the unwindowed path
+            sw = int(d.get("sliding_window") or 0) if mt == "mistral" else 0
+            sw = sw if 0 < sw < max_pos else 0
             return cls(
                 model_type="llama", vocab_size=d["vocab_size"], hidden_size=h, num_layers=d["num_hidden_layers"],
                 num_heads=nh, num_kv_heads=d.get("num_key_value_heads") or nh, head_dim=hd,
                 intermediate_size=d["intermediate_size"],
-                max_position_embeddings=d.get("max_position_embeddings", 4096),
+                max_position_embeddings=max_pos,
                 norm="rmsnorm", norm_eps=d.get("rms_norm_eps", 1e-6), activation="silu_glu", position="rope",
                 rope_style="neox", rotary_dim=hd, rope_theta=_rope_theta(d),
                 tie_word_embeddings=d.get("tie_word_embeddings", False),
                 qkv_bias=d.get("attention_bias", False), out_bias=d.get("attention_bias", False),
-                mlp_bias=d.get("mlp_bias", False), **common,
+                mlp_bias=d.get("mlp_bias", False), sliding_window=sw, **common,
             )
         raise ValueError(f"unsupported model_type {mt!r}; supported: gpt2, gptj, gpt_bigcode, llama")
 
@@ -200,6 +207,9 @@ _PRESETS: Dict[str, Dict[str, Any]] = {
     "llama2-70b": dict(model_type="llama", hidden_size=8192, num_hidden_layers=80, num_attention_heads=64,
                        num_key_value_heads=8, intermediate_size=28672, vocab_size=32000,
                        max_position_embeddings=4096),
+    "mistral-7b": dict(model_type="mistral", hidden_size=4096, num_hidden_layers=32, num_attention_heads=32,
+                       num_key_value_heads=8, intermediate_size=14336, vocab_size=32000,
+                       max_position_embeddings=32768, sliding_window=4096),
     # tiny shapes for tests
     "tiny-gpt2": dict(model_type="gpt2", n_embd=64, n_layer=2, n_head=4, n_positions=128, vocab_size=211),
     "tiny-gptj": dict(model_type="gptj", n_embd=64, n_layer=2, n_head=4, n_positions=128, vocab_size=211,
@@ -209,6 +219,10 @@ _PRESETS: Dict[str, Dict[str, Any]] = {
     "tiny-llama": dict(model_type="llama", hidden_size=64, num_hidden_layers=2, num_attention_heads=4,
                        num_key_value_heads=2, intermediate_size=160, vocab_size=211,
                        max_position_embeddings=128),
+    # head dim 64 (a paged-kernel size), window of two 16-token pages
+    "tiny-mistral": dict(model_type="mistral", hidden_size=256, num_hidden_layers=2, num_attention_heads=4,
+                         num_key_value_heads=2, intermediate_size=512, vocab_size=211,
+                         max_position_embeddings=256, sliding_window=32),
     # TP up to 8 (16 q / kv heads: 2 per rank at TP=8, as Llama-2-7B's 32 give 4)
     "tiny-llama16h": dict(model_type="llama", hidden_size=256, num_hidden_layers=2, num_attention_heads=16,
                           num_key_value_heads=16, intermediate_size=512, vocab_size=211,

@@ -51,6 +51,8 @@ class StepInput:
     are prompt chunks (cu_seqlens relative to row num_decode) that may continue a cached prefix
     (has_prefix: some chunk starts past position 0, so its attention reads the paged cache).
     block_tables / ctx_lens cover every sequence of the step, decodes first.
+    window (0 = full attention): a token at position p attends keys p - window < j <= p through the paged
+    kernels; kv_starts ([B] int32, optional): the first key of each sequence's table row that may be read.
     """
     kind: str  # "prefill" | "decode" | "extend"
     input_ids: torch.Tensor  # [T] int64
@@ -66,6 +68,8 @@ class StepInput:
     num_decode: int = 0  # extend: leading single-token decode rows
     has_prefix: bool = False  # extend: a prompt chunk continues a cached prefix
     cu_host: Optional[Sequence[int]] = None  # prefill: cu_seqlens on the host (micro-batch split points)
+    window: int = 0  # sliding-window attention: keys per query (a launch constant, so graphs capture it)
+    kv_starts: Optional[torch.Tensor] = None  # [B] int32 first readable key per sequence (PagedPast.truncate)
 
 
 class StreamLedger:
@@ -235,13 +239,14 @@ class DecoderLM:
             # o-projection's per-token fp8 input, so the W8A8 GEMM skips its own quantisation launch
             f8 = self._fp8_in(L.o, qkv) and _hip_ops().extend_fp8_twin_ok(p.nh_l, p.nkv_l)
             return ops.attn_extend(qkv, kc, vc, inp.block_tables, self.decode_cu(B, qkv.device), inp.ctx_lens, 1,
-                                   p.nh_l, p.nkv_l, D, self.scale, fp8_out=f8)
+                                   p.nh_l, p.nkv_l, D, self.scale, fp8_out=f8, window=inp.window,
+                                   kv_starts=inp.kv_starts)
         if inp.kind == "prefill":
             return ops.attn_prefill(qkv, inp.cu_seqlens, inp.max_seqlen, p.nh_l, p.nkv_l, D, self.scale)
         if inp.kind == "extend":
             return self._attention_extend(qkv, inp, kc, vc)
         return ops.attn_decode(qkv, kc, vc, inp.block_tables, inp.ctx_lens, p.nh_l, p.nkv_l, D, self.scale,
-                               inp.max_ctx, splits=inp.decode_splits)
+                               inp.max_ctx, splits=inp.decode_splits, window=inp.window, kv_starts=inp.kv_starts)
 
     def _attention_extend(self, qkv, inp: StepInput, kc, vc):
         """Mixed step: decode rows through the split-K decode kernel, prompt-chunk rows through the
@@ -251,11 +256,13 @@ class DecoderLM:
         out = torch.empty(T, p.nh_l * D, dtype=qkv.dtype, device=qkv.device)
         if nd:
             ops.attn_decode(qkv[:nd], kc, vc, inp.block_tables[:nd], inp.ctx_lens[:nd], p.nh_l, p.nkv_l, D,
-                            self.scale, inp.max_ctx, out=out[:nd])
+                            self.scale, inp.max_ctx, out=out[:nd], window=inp.window,
+                            kv_starts=None if inp.kv_starts is None else inp.kv_starts[:nd])
         if T > nd:
             if inp.has_prefix:
                 ops.attn_extend(qkv[nd:], kc, vc, inp.block_tables[nd:], inp.cu_seqlens, inp.ctx_lens[nd:],
-                                inp.max_seqlen, p.nh_l, p.nkv_l, D, self.scale, out=out[nd:])
+                                inp.max_seqlen, p.nh_l, p.nkv_l, D, self.scale, out=out[nd:], window=inp.window,
+                                kv_starts=None if inp.kv_starts is None else inp.kv_starts[nd:])
             else:
                 ops.attn_prefill(qkv[nd:], inp.cu_seqlens, inp.max_seqlen, p.nh_l, p.nkv_l, D, self.scale,
                                  out=out[nd:])
@@ -403,10 +410,13 @@ class DecoderLM:
     def _sub_step(self, inp: StepInput, r0: int, r1: int, block_size: int) -> StepInput:
         splits = inp.decode_splits
         if splits is not None and inp.input_ids.is_cuda:
-            splits = _hip_ops().decode_splits(r1 - r0, self.plan.nkv_l, inp.max_ctx, block_size)
+            H = _hip_ops()
+            splits = H.decode_splits(r1 - r0, self.plan.nkv_l, H.decode_span(inp.max_ctx, block_size, inp.window),
+                                     block_size)
         return StepInput("decode", inp.input_ids[r0:r1], inp.positions[r0:r1], inp.slots[r0:r1],
                          block_tables=inp.block_tables[r0:r1], ctx_lens=inp.ctx_lens[r0:r1], max_ctx=inp.max_ctx,
-                         decode_splits=splits)
+                         decode_splits=splits, window=inp.window,
+                         kv_starts=None if inp.kv_starts is None else inp.kv_starts[r0:r1])
 
     def _hidden_states_overlap(self, inp: StepInput, kv_caches, h: int, subs=None) -> torch.Tensor:
         """Decode step (or prefill step: ``subs`` from _sub_prefill) as two micro-batches (rows [0, h) and
@@ -514,6 +524,12 @@ class DecoderLM:
         return h
 
     def _hidden_states(self, inp: StepInput, kv_caches) -> torch.Tensor:
+        if inp.window > 0 and inp.max_seqlen > inp.window and (
+                inp.kind == "prefill" or (inp.kind == "extend" and not inp.has_prefix)):
+            # the flash prefill kernel has no lower mask: a prompt (or a first chunk) longer than the window would
+            # silently attend too many keys. Feed such a prompt in chunks of at most `window` tokens.
+            raise ValueError(f"a {inp.kind} step of {inp.max_seqlen} tokens exceeds the attention window "
+                             f"{inp.window}: windowed prompts run as chunks of at most the window")
         if inp.kind == "decode":
             B = inp.input_ids.shape[0]
             if self.rsag_ok(B) and (self.rsag_mode == "1" or B in self.rsag):

@@ -31,9 +31,36 @@ class CausalLMOutput:
 
 
 class PagedPast:
-    def __init__(self, lens, blocks):
+    def __init__(self, lens, blocks, offs=None, pool=None):
         self.lens = lens  # tokens cached per row
         self.blocks = blocks  # list of block-id lists per row
+        self.offs = offs if offs is not None else [0] * len(lens)  # in-page offset of each row's first kept key
+        self._block_size = 0  # set by the CausalLM call that fills the blocks
+        self._pool = pool  # the owning CausalLM's free list (truncate returns blocks to it)
+
+    def truncate(self, keep_last: int) -> "PagedPast":
+        """Keep the last ``keep_last`` cached keys of every row, at any token boundary - the reference caller's KV
+        window (``generate.py:132-142``: ``past[..., -(n_positions - 1):, :]``). Wholly dropped blocks go back to
+        the pool and the row's block list is rebased; the first kept key's offset inside its page is recorded and
+        reaches the attention kernels as ``kv_starts``. The next call's default positions are the kept length,
+        as in the reference (``gptj_modeling.py:423-431``)."""
+        if keep_last < 0:
+            raise ValueError("truncate: keep_last must be >= 0")
+        for b, n in enumerate(self.lens):
+            drop = n - keep_last
+            if drop <= 0:
+                continue
+            bs = self._block_size
+            first = self.offs[b] + drop  # table index of the first kept key
+            gone = first // bs if keep_last > 0 else len(self.blocks[b])
+            if gone:
+                if self._pool is None:
+                    raise RuntimeError("truncate: this PagedPast was not produced by a CausalLM call")
+                self._pool.extend(self.blocks[b][:gone])
+                self.blocks[b] = self.blocks[b][gone:]
+            self.offs[b] = first % bs if keep_last > 0 else 0
+            self.lens[b] = keep_last
+        return self
 
 
 class CausalLM:
@@ -90,6 +117,7 @@ class CausalLM:
         B, S = input_ids.shape
         bs = self.block_size
         past = past_key_values or PagedPast([0] * B, [[] for _ in range(B)])
+        past._pool, past._block_size = self._free, bs
         if attention_mask is not None:
             am = attention_mask.to("cpu").bool()
             if am.shape[0] != B or am.shape[1] < S:
@@ -110,28 +138,47 @@ class CausalLM:
         out = torch.zeros(B, S, self.model.plan.vocab_padded, dtype=torch.float32, device=dev)
         if order:
             # the whole step's block need first: a failed allocation then leaves the pool untouched
-            needs = [max(0, -(-(start + len(cols)) // bs) - len(past.blocks[b])) for b, cols, start in order]
+            # a row's keys sit at table indices [offs, offs + len): a truncated row starts inside its first page
+            needs = [max(0, -(-(past.offs[b] + start + len(cols)) // bs) - len(past.blocks[b]))
+                     for b, cols, start in order]
             if sum(needs) > len(self._free):
                 raise RuntimeError("CausalLM: KV pool exhausted")
+            # positions are checked against the wpe / RoPE table on the host, before anything is allocated or
+            # launched (the kernels index the tables unchecked)
+            table = self.model.w.wpe if self.model.w.wpe is not None else self.model.w.cos
+            if table is not None:
+                for b, cols, start in order:
+                    hi = int(pos_cpu[b, cols].max()) if pos_cpu is not None else start + len(cols) - 1
+                    lo = int(pos_cpu[b, cols].min()) if pos_cpu is not None else start
+                    if lo < 0 or hi >= table.shape[0]:
+                        raise ValueError(f"position {hi if hi >= table.shape[0] else lo} of row {b} is outside the "
+                                         f"model's {table.shape[0]} positions (truncate the cache to continue)")
             for (b, _, _), need in zip(order, needs):
                 if need:
                     past.blocks[b].extend(self._alloc(need))
-            tok, pos, slots, qlens, ctx, bt_rows = [], [], [], [], [], []
+            tok, pos, slots, qlens, ctx, bt_rows, kvs = [], [], [], [], [], [], []
             for b, cols, start in order:
                 n = len(cols)
                 blocks = past.blocks[b]
+                off = past.offs[b]
                 tok.append(ids_cpu[b, cols])
                 pos.append(pos_cpu[b, cols] if pos_cpu is not None else torch.arange(start, start + n))
-                slots += [blocks[p // bs] * bs + p % bs for p in range(start, start + n)]
+                slots += [blocks[p // bs] * bs + p % bs for p in range(off + start, off + start + n)]
                 qlens.append(n)
-                ctx.append(start + n)
+                ctx.append(off + start + n)
                 bt_rows.append(blocks)
+                kvs.append(off)
             nd = len(dec)
             qt = torch.tensor(qlens)
             ends = qt.cumsum(0)
             cu = torch.zeros(len(ext) + 1, dtype=torch.int32)
             cu[1:] = (ends[nd:] - (ends[nd - 1] if nd else 0)).to(torch.int32)
             has_prefix = any(start > 0 for _, _, start in ext)
+            # rows cut inside their first page hand the kernels their first readable key; none cut: the plain call
+            kv_starts = torch.tensor(kvs, dtype=torch.int32, device=dev) if any(kvs) else None
+            if kv_starts is not None:
+                has_prefix = True  # the paged extend kernel (the flash prefill kernel has no lower bound)
+            window = int(self.config.sliding_window)
             maxb = max(len(r) for r in bt_rows)
             bt = torch.zeros(len(order), maxb, dtype=torch.int32)
             for i, r in enumerate(bt_rows):
@@ -141,10 +188,10 @@ class CausalLM:
                             torch.tensor(slots, dtype=torch.int64, device=dev), cu_seqlens=cu.to(dev),
                             max_seqlen=int(qt[nd:].max()) if ext else 0, block_tables=bt.to(dev),
                             ctx_lens=torch.tensor(ctx, dtype=torch.int32, device=dev), max_ctx=maxb * bs,
-                            num_decode=nd, has_prefix=has_prefix)
+                            num_decode=nd, has_prefix=has_prefix, window=window, kv_starts=kv_starts)
             if kind == "extend" and not ext:  # decodes only
                 inp = StepInput("decode", inp.input_ids, inp.positions, inp.slots, block_tables=inp.block_tables,
-                                ctx_lens=inp.ctx_lens, max_ctx=inp.max_ctx)
+                                ctx_lens=inp.ctx_lens, max_ctx=inp.max_ctx, window=window, kv_starts=kv_starts)
             logits = self.model.logits(self.model.hidden_states(inp, self.kv)).float()
             r0 = 0
             for (b, cols, start), n in zip(order, qlens):
@@ -244,8 +291,15 @@ class GPT2LMHeadModel(_FamilyLM):
 
 
 class LlamaForCausalLM(_FamilyLM):
+    """Llama and Mistral checkpoints (``model_type`` "mistral" parses to the llama family plus ``sliding_window``)."""
     model_type = "llama"
 
 
+class MistralForCausalLM(_FamilyLM):
+    """Mistral checkpoints: the llama decoder with ``sliding_window`` attention (a query at position p attends keys
+    p - W < j <= p); a prompt longer than the window is fed in calls of at most W tokens."""
+    model_type = "mistral"
+
+
 MODEL_REGISTRY = {c.model_type: c for c in (GPT2LMHeadModel, GPTJForCausalLM, GPTBigCodeForCausalLM,
-                                            LlamaForCausalLM)}
+                                            LlamaForCausalLM, MistralForCausalLM)}

@@ -65,21 +65,27 @@ def attn_prefill(qkv, cu_seqlens, max_seqlen, nh, nkv, D, scale, out=None):
     return _into(ref.attn_prefill(qkv, cu_seqlens, nh, nkv, D, scale), out)
 
 
-def attn_decode(q, k_cache, v_cache, block_tables, ctx_lens, nh, nkv, D, scale, max_ctx, splits=None, out=None):
+def attn_decode(q, k_cache, v_cache, block_tables, ctx_lens, nh, nkv, D, scale, max_ctx, splits=None, out=None,
+                window=0, kv_starts=None):
+    """``window`` (0 = unlimited) / ``kv_starts`` [B] int32: row b attends keys
+    ``[max(kv_starts[b], ctx_b - window), ctx_b)`` (sliding-window attention; a cache cut inside its first page)."""
     if q.is_cuda:
         return _hip().attn_decode(q, k_cache, v_cache, block_tables, ctx_lens, nh, nkv, D, scale, max_ctx,
-                                  splits=splits, out=out)
-    return _into(ref.attn_decode(q, k_cache, v_cache, block_tables, ctx_lens, nh, nkv, D, scale), out)
+                                  splits=splits, out=out, window=window, kv_starts=kv_starts)
+    return _into(ref.attn_decode(q, k_cache, v_cache, block_tables, ctx_lens, nh, nkv, D, scale, window=window,
+                                 kv_starts=kv_starts), out)
 
 
 def attn_extend(q, k_cache, v_cache, block_tables, cu_q, ctx_lens, max_qlen, nh, nkv, D, scale, out=None,
-                fp8_out=False):
+                fp8_out=False, window=0, kv_starts=None):
     """Chunked-prefill attention over the paged cache (the chunk's K/V already written). ``fp8_out``: the GPU
-    kernel also writes the per-token fp8 twin for a W8A8 consumer (ops.hip.attn_extend); ignored on the CPU."""
+    kernel also writes the per-token fp8 twin for a W8A8 consumer (ops.hip.attn_extend); ignored on the CPU.
+    ``window`` / ``kv_starts``: the row at position p attends keys ``[max(kv_starts[b], p - window + 1), p]``."""
     if q.is_cuda:
         return _hip().attn_extend(q, k_cache, v_cache, block_tables, cu_q, ctx_lens, max_qlen, nh, nkv, D, scale,
-                                  out=out, fp8_out=fp8_out)
-    return _into(ref.attn_extend(q, k_cache, v_cache, block_tables, cu_q, ctx_lens, nh, nkv, D, scale), out)
+                                  out=out, fp8_out=fp8_out, window=window, kv_starts=kv_starts)
+    return _into(ref.attn_extend(q, k_cache, v_cache, block_tables, cu_q, ctx_lens, nh, nkv, D, scale, window=window,
+                                 kv_starts=kv_starts), out)
 
 
 def linear(x, w, bias=None, act="none", glu=False, w_scale: Optional[torch.Tensor] = None, partial_ok=False):

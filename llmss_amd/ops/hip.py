@@ -193,13 +193,25 @@ def extend_fp8_twin_ok(nh: int, nkv: int) -> bool:
     return nkv == 1 and G <= 16 and G & (G - 1) == 0
 
 
+def _kv_starts_check(kv_starts, B: int, window: int) -> int:
+    """``kv_starts`` [>= B] int32 (the first key a sequence may attend) is validated like ``ctx_lens``."""
+    _check(int(window) >= 0, "window must be >= 0")
+    if kv_starts is None:
+        return 0
+    _check(kv_starts.dtype == torch.int32 and kv_starts.is_contiguous() and kv_starts.is_cuda
+           and kv_starts.numel() >= B, "kv_starts must be contiguous int32 cuda with >= B entries")
+    _check(kv_starts.device.index == torch.cuda.current_device(), "kv_starts on the current device")
+    return kv_starts.data_ptr()
+
+
 def attn_extend(q, k_cache, v_cache, block_tables, cu_q, ctx_lens, max_qlen, nh, nkv, D, scale, out=None,
-                fp8_out=False):
+                fp8_out=False, window=0, kv_starts=None):
     """Chunked-prefill attention: q rows [T, >= nh*D] (query heads first, as in the QKV output) of B
     sequences (``cu_q`` [B+1] int32), each attending its whole paged context ``ctx_lens`` [B] int32 (the
     chunk's own K/V already written to the cache) causally. ``fp8_out`` (only where extend_fp8_twin_ok):
     also write the output's per-token fp8 twin for the W8A8 o-projection, which then skips its quantisation
-    launch."""
+    launch. ``window`` (0 = unlimited) / ``kv_starts`` [B] int32: the row at position p attends keys
+    ``[max(kv_starts[b], p - window + 1), p]``; nothing below that range's first page is read from the table."""
     T = q.shape[0]
     _bf16_rows(q, "q")
     _check(q.shape[1] >= nh * D, "q too narrow")
@@ -215,13 +227,15 @@ def attn_extend(q, k_cache, v_cache, block_tables, cu_q, ctx_lens, max_qlen, nh,
     y = out if out is not None else torch.empty(T, nh * D, dtype=q.dtype, device=q.device)
     _bf16_rows(y, "out")
     _check(y.shape[0] >= T and y.shape[1] >= nh * D, "out shape")
+    kvs = _kv_starts_check(kv_starts, B, window)
     q8 = s8 = None
     if fp8_out:
         _check(extend_fp8_twin_ok(nh, nkv) and y.shape == (T, nh * D), "fp8 twin: one kv head, group <= 16, dense out")
         q8, s8 = _fp8_twin(y)
     lib().attn_extend(q.data_ptr(), q.stride(0), k_cache.data_ptr(), v_cache.data_ptr(), block_tables.data_ptr(),
                       block_tables.shape[1], cu_q.data_ptr(), ctx_lens.data_ptr(), y.data_ptr(), y.stride(0), B,
-                      int(max_qlen), nh, nkv, D, bs, float(scale), _stream(), kv8, _ptr(q8), _ptr(s8))
+                      int(max_qlen), nh, nkv, D, bs, float(scale), _stream(), kv8, _ptr(q8), _ptr(s8),
+                      int(window), kvs)
     return y
 
 
@@ -319,8 +333,15 @@ class workspace_slot:
 _DECODE_WS = _Slotted(DecodeWorkspace)
 
 
+def decode_span(max_ctx: int, block_size: int, window: int = 0) -> int:
+    """Keys the decode partitions have to cover: a windowed row reads ``[lo, ctx)`` and its partitions start at
+    lo's page, so at most ``window + block_size`` keys however long the context is."""
+    return min(max_ctx, window + block_size) if window > 0 else max_ctx
+
+
 def decode_splits(B: int, nkv: int, max_ctx: int, block_size: int) -> tuple:
-    """(num_splits, partition_size): ~8 workgroups per CU (2048), partitions >= 256 tokens.
+    """(num_splits, partition_size): ~8 workgroups per CU (2048), partitions >= 256 tokens. ``max_ctx`` is the
+    span to cover (:func:`decode_span` for a windowed call).
 
     Measured (bench/attn_bench.py): with few (sequence, kv-head) pairs - GQA / TP-sharded kv heads -
     each workgroup otherwise walks the whole context serially and the KV stream drops to 2-3 TB/s."""
@@ -333,7 +354,10 @@ def decode_splits(B: int, nkv: int, max_ctx: int, block_size: int) -> tuple:
     return nsplit, psize
 
 
-def attn_decode(q, k_cache, v_cache, block_tables, ctx_lens, nh, nkv, D, scale, max_ctx, out=None, splits=None):
+def attn_decode(q, k_cache, v_cache, block_tables, ctx_lens, nh, nkv, D, scale, max_ctx, out=None, splits=None,
+                window=0, kv_starts=None):
+    """``window`` (0 = unlimited) / ``kv_starts`` [B] int32: row b attends keys ``[lo, ctx_b)`` with
+    ``lo = max(kv_starts[b], ctx_b - window)``; the splits are laid from lo's page and cover :func:`decode_span`."""
     B = q.shape[0]
     _check(q.is_cuda and q.dtype == torch.bfloat16 and q.stride(-1) == 1 and q.dim() == 2, "q [B, >=nh*D]")
     _check(q.shape[1] >= nh * D, "q too narrow")
@@ -344,15 +368,17 @@ def attn_decode(q, k_cache, v_cache, block_tables, ctx_lens, nh, nkv, D, scale, 
     _check(ctx_lens.dtype == torch.int32 and ctx_lens.numel() >= B and ctx_lens.is_contiguous(), "ctx_lens int32")
     bs = k_cache.shape[2]
     _check(block_tables.shape[1] * bs >= max_ctx, "block table too short for max_ctx")
-    nsplit, psize = splits if splits is not None else decode_splits(B, nkv, max_ctx, bs)
-    _check(nsplit * psize >= max_ctx, "splits do not cover max_ctx")
+    kvs = _kv_starts_check(kv_starts, B, window)
+    span = decode_span(max_ctx, bs, int(window))
+    nsplit, psize = splits if splits is not None else decode_splits(B, nkv, span, bs)
+    _check(nsplit >= 1 and psize >= 1 and nsplit * psize >= span, "splits do not cover max_ctx")
     y = out if out is not None else torch.empty(B, nh * D, dtype=q.dtype, device=q.device)
     _bf16_rows(y, "out")
     _check(y.shape[0] >= B and y.shape[1] >= nh * D, "out shape")
     po, pml = _DECODE_WS.get(B, nh, nsplit, D, q.device) if nsplit > 1 else (None, None)
     lib().attn_decode(q.data_ptr(), q.stride(0), k_cache.data_ptr(), v_cache.data_ptr(), block_tables.data_ptr(),
                       block_tables.stride(0), ctx_lens.data_ptr(), y.data_ptr(), y.stride(0), _ptr(po), _ptr(pml),
-                      B, nh, nkv, D, bs, nsplit, psize, float(scale), _stream(), kv8)
+                      B, nh, nkv, D, bs, nsplit, psize, float(scale), _stream(), kv8, int(window), kvs)
     return y
 
 

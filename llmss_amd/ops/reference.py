@@ -187,20 +187,34 @@ def gather_kv(cache: torch.Tensor, block_table_row: torch.Tensor, ctx: int) -> t
     return kv_rows_dequant(out, cache.shape[3] - KV8_TAIL) if cache.dtype == torch.uint8 else out
 
 
+def gather_kv_range(cache: torch.Tensor, block_table_row: torch.Tensor, lo: int, ctx: int) -> torch.Tensor:
+    """Keys ``[lo, ctx)`` of one sequence as [nkv, ctx - lo, D]; table entries below lo's page are never read
+    (a windowed sequence's released pages leave stale ids there)."""
+    bs = cache.shape[2]
+    pg = lo // bs
+    return gather_kv(cache, block_table_row[pg:], ctx - pg * bs)[:, lo - pg * bs:]
+
+
+def _kv_lo(kv_starts, b: int) -> int:
+    return 0 if kv_starts is None else int(kv_starts[b])
+
+
 def attn_decode(q: torch.Tensor, k_cache, v_cache, block_tables, ctx_lens, nh: int, nkv: int, D: int,
-                scale: float) -> torch.Tensor:
-    """q [B, >= nh*D] (row-strided view allowed); returns [B, nh*D]."""
+                scale: float, window: int = 0, kv_starts=None) -> torch.Tensor:
+    """q [B, >= nh*D] (row-strided view allowed); returns [B, nh*D]. Row b attends keys ``[lo, ctx_b)`` with
+    ``lo = max(kv_starts[b], ctx_b - window)`` (``window`` 0 = unlimited)."""
     B = q.shape[0]
     g = nh // nkv
     out = torch.empty(B, nh * D, dtype=q.dtype, device=q.device)
     for b in range(B):
         ctx = int(ctx_lens[b])
         qq = q[b, : nh * D].view(nh, D).float()
-        if ctx == 0:
+        lo = max(_kv_lo(kv_starts, b), ctx - window if window > 0 else 0, 0)
+        if ctx <= lo:
             out[b] = 0
             continue
-        k = gather_kv(k_cache, block_tables[b], ctx).float().repeat_interleave(g, 0)  # [nh, ctx, D]
-        v = gather_kv(v_cache, block_tables[b], ctx).float().repeat_interleave(g, 0)
+        k = gather_kv_range(k_cache, block_tables[b], lo, ctx).float().repeat_interleave(g, 0)  # [nh, ctx - lo, D]
+        v = gather_kv_range(v_cache, block_tables[b], lo, ctx).float().repeat_interleave(g, 0)
         s = torch.einsum("hd,htd->ht", qq, k) * scale
         p = torch.softmax(s, -1)
         out[b] = torch.einsum("ht,htd->hd", p, v).reshape(-1).to(q.dtype)
@@ -208,9 +222,10 @@ def attn_decode(q: torch.Tensor, k_cache, v_cache, block_tables, ctx_lens, nh: i
 
 
 def attn_extend(q: torch.Tensor, k_cache, v_cache, block_tables, cu_q, ctx_lens, nh: int, nkv: int, D: int,
-                scale: float) -> torch.Tensor:
+                scale: float, window: int = 0, kv_starts=None) -> torch.Tensor:
     """Chunked prefill over the paged cache: sequence b's rows cu_q[b]:cu_q[b+1] sit at positions
-    ctx_lens[b] - qlen ... ctx_lens[b] - 1 and attend every cached key up to their own position."""
+    ctx_lens[b] - qlen ... ctx_lens[b] - 1 and attend every cached key up to their own position; with
+    ``window`` / ``kv_starts`` the row at position p attends keys ``[max(kv_starts[b], p - window + 1), p]``."""
     T = q.shape[0]
     g = nh // nkv
     out = torch.zeros(T, nh * D, dtype=q.dtype, device=q.device)
@@ -222,12 +237,22 @@ def attn_extend(q: torch.Tensor, k_cache, v_cache, block_tables, cu_q, ctx_lens,
         ctx = int(ctx_lens[b])
         p0 = ctx - (e - a)
         qq = q[a:e, : nh * D].view(e - a, nh, D).float().transpose(0, 1)  # [nh, q, D]
-        k = gather_kv(k_cache, block_tables[b], ctx).float().repeat_interleave(g, 0)  # [nh, ctx, D]
-        v = gather_kv(v_cache, block_tables[b], ctx).float().repeat_interleave(g, 0)
+        kvs = max(_kv_lo(kv_starts, b), 0)
+        lo = max(kvs, p0 - window + 1 if window > 0 else 0)  # the lowest row's first key
+        if ctx <= lo:
+            continue
+        k = gather_kv_range(k_cache, block_tables[b], lo, ctx).float().repeat_interleave(g, 0)  # [nh, ctx - lo, D]
+        v = gather_kv_range(v_cache, block_tables[b], lo, ctx).float().repeat_interleave(g, 0)
         s = torch.matmul(qq, k.transpose(1, 2)) * scale
         qpos = torch.arange(p0, ctx, device=q.device)[:, None]
-        s = s.masked_fill(torch.arange(ctx, device=q.device)[None, :] > qpos, float("-inf"))
-        out[a:e] = torch.matmul(torch.softmax(s, -1), v).transpose(0, 1).reshape(e - a, nh * D).to(q.dtype)
+        key = torch.arange(lo, ctx, device=q.device)[None, :]
+        dead = key > qpos
+        if window > 0:
+            dead = dead | (key < qpos - window + 1)
+        s = s.masked_fill(dead, float("-inf"))
+        # a row without any key (kv_starts above its position) gives 0, as the kernels do
+        p = torch.nan_to_num(torch.softmax(s, -1), nan=0.0) if bool(dead.all(1).any()) else torch.softmax(s, -1)
+        out[a:e] = torch.matmul(p, v).transpose(0, 1).reshape(e - a, nh * D).to(q.dtype)
     return out
 
 
