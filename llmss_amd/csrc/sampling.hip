@@ -32,6 +32,13 @@ __device__ __forceinline__ unsigned philox(unsigned c0, unsigned c1, unsigned k0
   return c0;
 }
 
+// Uniform in (0, 1) from the top 24 bits of a Philox word. (float)m + 0.5f rounds to even once m >= 2^23, so
+// m = 0xFFFFFF would give exactly 1.0f - a Gumbel value of +inf, and that token wins whatever its logit: clamp
+// to the largest float below 1. Every other draw is unchanged (ops/reference.py _select has the same mapping).
+__device__ __forceinline__ float gumbel_u(unsigned r) {
+  return fminf(((float)(r >> 8) + 0.5f) * (1.0f / 16777216.0f), 0x1.fffffep-1f);
+}
+
 template <typename T>
 __device__ __forceinline__ float load_logit(const T* p, int i);
 template <>
@@ -126,7 +133,7 @@ __global__ __launch_bounds__(1024) void sample_kernel(const T* __restrict__ logi
     if (!greedy) {
       if (fkey(x) < thr) continue;
       const unsigned r = philox((unsigned)i, (unsigned)b * 0u, s0, s1);
-      const float u = ((float)(r >> 8) + 0.5f) * (1.0f / 16777216.0f);
+      const float u = gumbel_u(r);
       v = x - __logf(-__logf(u));
     }
     if (v > best || (v == best && i < besti)) { best = v; besti = i; }
@@ -421,7 +428,7 @@ FOR_ELEMS(i) {
     if (!greedy) {
       if (v < thr) continue;
       const unsigned r = philox((unsigned)idx, 0u, s0, s1);
-      const float u = ((float)(r >> 8) + 0.5f) * (1.0f / 16777216.0f);
+      const float u = gumbel_u(r);
       v = v - __logf(-__logf(u));
     }
     if (v > best || (v == best && idx < besti)) { best = v; besti = idx; }
@@ -771,7 +778,7 @@ __global__ __launch_bounds__(256) void sample_cand_kernel(const float* __restric
     if (!greedy) {
       if (x < thr) continue;
       const unsigned r = philox((unsigned)idx, 0u, s0, s1);
-      const float u = ((float)(r >> 8) + 0.5f) * (1.0f / 16777216.0f);
+      const float u = gumbel_u(r);
       x = x - __logf(-__logf(u));
     }
     if (x > best || (x == best && idx < besti)) { best = x; besti = idx; }

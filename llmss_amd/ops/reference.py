@@ -374,6 +374,14 @@ def _mass(x: np.ndarray, mx: np.float32) -> np.ndarray:
     return (np.exp((x - mx).astype(np.float32)).astype(np.float32) * np.float32(4294967296.0)).astype(np.uint64)
 
 
+def _gumbel_u(r: np.ndarray) -> np.ndarray:
+    """Uniform in (0, 1) from the top 24 bits of a Philox word, in fp32 exactly as csrc/sampling.hip gumbel_u:
+    m + 0.5 rounds to even once m >= 2^23, so m = 0xFFFFFF would give 1.0 (a Gumbel value of +inf); clamped to
+    the largest fp32 below 1."""
+    u = ((r >> np.uint64(8)).astype(np.float32) + np.float32(0.5)) * np.float32(1.0 / 16777216.0)
+    return np.minimum(u, np.nextafter(np.float32(1), np.float32(0)))
+
+
 def _select(x: np.ndarray, idx: np.ndarray, t: float, k: int, p: float, seed: int, V: int) -> int:
     """One row: x = scaled logits of the (candidate) elements, idx their global token ids."""
     valid = np.isfinite(x) | (x > -np.inf)
@@ -402,7 +410,7 @@ def _select(x: np.ndarray, idx: np.ndarray, t: float, k: int, p: float, seed: in
         keep = x >= thr
         v, idx = v[keep], idx[keep]
         r = philox(idx, seed)
-        u = ((r >> np.uint64(8)).astype(np.float32) + np.float32(0.5)) * np.float32(1.0 / 16777216.0)
+        u = _gumbel_u(r)
         v = (v - np.log(-np.log(u))).astype(np.float32)
     best = v.max()
     return int(idx[v == best].min())
@@ -437,7 +445,9 @@ def cand_topk(local: torch.Tensor, lo: int, V: int, temperature, top_k, K: int, 
         n = max(0, min(vl, V - lo))
         x = lg[b, :n].astype(np.float32) * sc
         kth = np.sort(x)[::-1][K - 1] if n >= K else -np.inf
-        sel = np.flatnonzero(x >= kth)[:KC]
+        # more than KC at or above the boundary (ties, or -inf when the shard has fewer than K finite logits): every
+        # element above it first, then the ties in ascending index, as the kernel's rewrite of such a row does
+        sel = np.concatenate([np.flatnonzero(x > kth), np.flatnonzero(x == kth)])[:KC]
         vals = np.full(KC, -np.inf, dtype=np.float32)
         ids = np.full(KC, 0x7FFFFFFF, dtype=np.int32)
         vals[:sel.size] = x[sel]
