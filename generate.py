@@ -39,11 +39,15 @@ def get_args(argv=None):
     parser.add_argument("--seed", type=int, default=None)
     parser.add_argument("--device", type=str, default=None, help="cuda | cpu (default: cuda if available)")
     parser.add_argument("--json_metrics", action="store_true")
+    parser.add_argument("--logprobs", type=int, default=None,
+                        help="print, per generated token, its log-probability under the raw model distribution and the "
+                             "N most likely tokens (0..20; 0: the token's alone)")
     return parser.parse_args(argv)
 
 
-def recompute_generate(model, prompts, params, eos):
-    """Reference no-cache mode: every step re-runs the full prefix of every sequence."""
+def recompute_generate(model, prompts, params, eos, lp_out=None):
+    """Reference no-cache mode: every step re-runs the full prefix of every sequence. ``lp_out`` (one list per
+    prompt, with params.logprobs set): receives each generated token's (log-probability, [(id, log-probability)])."""
     from llmss_amd import ops
     from llmss_amd.engine.sampling import step_seed
     from llmss_amd.models.decoder import StepInput
@@ -71,7 +75,13 @@ def recompute_generate(model, prompts, params, eos):
         topk = torch.full((n,), params.k_top_k, dtype=torch.int32, device=dev)
         topp = torch.full((n,), params.k_top_p, dtype=torch.float32, device=dev)
         seeds = torch.tensor([step_seed(params.resolved_seed() + i, step) for i in live], dtype=torch.int64, device=dev)
-        tok = ops.sample(logits, temp, topk, topp, seeds, vocab=model.cfg.vocab_size).tolist()
+        tok = ops.sample(logits, temp, topk, topp, seeds, vocab=model.cfg.vocab_size)
+        if lp_out is not None:
+            nlp = params.logprobs
+            lp, top, tids = (x.cpu().tolist() for x in ops.token_logprobs(logits, model.cfg.vocab_size, tok, nlp))
+            for j, i in enumerate(live):
+                lp_out[i].append((lp[j], [(a, b) for a, b in zip(tids[j], top[j]) if a >= 0]))
+        tok = tok.tolist()
         for i, t in zip(live, tok):
             seqs[i].append(t)
             outs[i].append(t)
@@ -86,6 +96,7 @@ def main(argv=None):
     assert 0.0 < args.temperature <= 1.0, "Value of temperature is not valid."
     assert 0.0 < args.top_p <= 1.0, "Value of top_p is not valid."
     assert args.top_k >= 0, "Value of top_k is not valid."
+    assert args.logprobs is None or 0 <= args.logprobs <= 20, "Value of logprobs is not valid."
 
     from llmss_amd.engine import LLMEngine, SamplingParams, build_model
     from llmss_amd.parallel.dist import initialize_distributed
@@ -107,7 +118,8 @@ def main(argv=None):
     if seed is None:  # one seed for all ranks so they sample identically
         seed = tp.broadcast_object(int.from_bytes(os.urandom(4), "little") if rank == 0 else None)
     params = SamplingParams(max_new_tokens=args.max_new_tokens, is_greedy=args.is_greedy,
-                            temperature=args.temperature, top_p=args.top_p, top_k=args.top_k, seed=seed)
+                            temperature=args.temperature, top_p=args.top_p, top_k=args.top_k, seed=seed,
+                            logprobs=args.logprobs)
     eos = getattr(tokenizer, "eos_token_id", None)
     prompts = [encode(tokenizer, p) for p in args.prompts]
     max_len = model.cfg.max_position_embeddings
@@ -115,11 +127,23 @@ def main(argv=None):
 
     t0 = time.time()
     if args.use_cache:
-        engine = LLMEngine(model, max_num_seqs=max(1, len(prompts)), eos_token_id=eos)
+        engine = LLMEngine(model, max_num_seqs=max(1, len(prompts)), eos_token_id=eos,
+                           # --logprobs 0 still needs the kernel, hence an engine with N >= 1
+                           max_logprobs=0 if args.logprobs is None else max(1, args.logprobs))
         per = [SamplingParams(**{**params.__dict__, "seed": seed + i}) for i in range(len(prompts))]
-        outputs = engine.generate(prompts, per)
+        if args.logprobs is None:
+            outputs = engine.generate(prompts, per)
+        else:  # the engine's own loop, keeping the finished requests for their log-probabilities
+            rids = [engine.add_request(p, sp) for p, sp in zip(prompts, per)]
+            fin = {}
+            while engine.has_unfinished():
+                engine.step()
+                fin.update((r.id, r) for r in engine.pop_finished())
+            outputs = [fin[i].output_ids for i in rids]
+            logprobs = [list(zip(fin[i].output_logprobs, fin[i].output_top_logprobs)) for i in rids]
     else:
-        outputs = recompute_generate(model, prompts, params, eos)
+        logprobs = [[] for _ in prompts] if args.logprobs is not None else None
+        outputs = recompute_generate(model, prompts, params, eos, lp_out=logprobs)
     gen_s = time.time() - t0
 
     if rank == 0:
@@ -130,6 +154,12 @@ def main(argv=None):
         n = sum(len(o) for o in outputs)
         print(f"load time: {load_done - start_time:.3f} s, generation: {gen_s:.3f} s, "
               f"{n} tokens, {n / max(gen_s, 1e-9):.1f} tokens/s (tp={world_size}, {device.type}, {dtype})")
+        if args.logprobs is not None:  # one line per generated token, after the lines above
+            for p, (out, lps) in enumerate(zip(outputs, logprobs)):
+                for t, (tok, (lp, top)) in enumerate(zip(out, lps)):
+                    print("logprobs: " + json.dumps({
+                        "prompt": p, "position": t, "token_id": tok, "text": tokenizer.decode([tok]), "logprob": lp,
+                        "top": [[i, tokenizer.decode([i]), v] for i, v in top]}, ensure_ascii=False))
         if args.json_metrics:
             print(json.dumps({"load_s": load_done - start_time, "generate_s": gen_s, "tokens": n,
                               "tokens_per_s": n / max(gen_s, 1e-9), "tp": world_size}))

@@ -35,6 +35,11 @@ void launch_sample_cand(const void* pack, int64_t ldp, int B, int groups, int KC
                         const void* top_k, const void* top_p, const void* seeds, void* out, void* out2, hipStream_t st);
 void launch_ce_loss(const void* logits, int64_t ld, bool fp32, const void* labels, int T, int V, void* loss,
                     hipStream_t st);
+void launch_token_logprobs(const void* logits, int64_t ld, bool fp32, int B, int width, int lo, int V,
+                           const void* tokens, int N, int shards, void* lp, int64_t ld_lp, void* top_lp,
+                           int64_t ld_top, void* top_ids, int64_t ld_ids, void* pack, int64_t ldp, hipStream_t st);
+void launch_logprobs_combine(const void* pack, int64_t ldp, int B, int groups, int N, void* lp, int64_t ld_lp,
+                             void* top_lp, int64_t ld_top, void* top_ids, int64_t ld_ids, hipStream_t st);
 void launch_attn_extend(const void* q, int64_t q_stride, const void* k_cache, const void* v_cache,
                         const void* block_tables, int max_blocks, const void* cu_q, const void* ctx_lens, void* out,
                         int64_t out_stride, int B, int max_qlen, int nh, int nkv, int D, int bs, float scale,
@@ -127,6 +132,16 @@ PYBIND11_MODULE(_C, m) {
   });
   m.def("ce_loss", [](uintptr_t lg, int64_t ld, bool fp32, uintptr_t lab, int T, int V, uintptr_t loss, uintptr_t st) {
     launch_ce_loss(CP(lg), ld, fp32, CP(lab), T, V, P(loss), S(st));
+  });
+  m.def("token_logprobs", [](uintptr_t lg, int64_t ld, bool fp32, int B, int width, int lo, int V, uintptr_t tok, int N,
+                             int shards, uintptr_t lp, int64_t ld_lp, uintptr_t tlp, int64_t ld_top, uintptr_t tid,
+                             int64_t ld_ids, uintptr_t pack, int64_t ldp, uintptr_t st) {
+    launch_token_logprobs(CP(lg), ld, fp32, B, width, lo, V, CP(tok), N, shards, P(lp), ld_lp, P(tlp), ld_top, P(tid),
+                          ld_ids, P(pack), ldp, S(st));
+  });
+  m.def("logprobs_combine", [](uintptr_t pack, int64_t ldp, int B, int groups, int N, uintptr_t lp, int64_t ld_lp,
+                               uintptr_t tlp, int64_t ld_top, uintptr_t tid, int64_t ld_ids, uintptr_t st) {
+    launch_logprobs_combine(CP(pack), ldp, B, groups, N, P(lp), ld_lp, P(tlp), ld_top, P(tid), ld_ids, S(st));
   });
   m.def("attn_extend", [](uintptr_t q, int64_t qs, uintptr_t kc, uintptr_t vc, uintptr_t bt, int maxb, uintptr_t cu,
                           uintptr_t cl, uintptr_t out, int64_t os, int B, int maxq, int nh, int nkv, int D, int bs,

@@ -24,7 +24,7 @@ import math
 import os
 import time
 from dataclasses import dataclass, field
-from typing import Dict, Iterable, List, Optional, Sequence
+from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -35,7 +35,7 @@ from ..ops import hip as _hip_ops
 from ..utils.logging import get_logger
 from ..utils.tracing import PhaseTimer
 from ..utils.tracing import range as trace_range
-from .sampling import SamplingParams, step_seeds
+from .sampling import MAX_TOP_LOGPROBS, SamplingParams, step_seeds
 
 log = get_logger(__name__)
 
@@ -57,6 +57,10 @@ class Request:
     t_first: float = 0.0
     t_last: float = 0.0
     token_times: List[float] = field(default_factory=list)
+    # params.logprobs is not None: parallel to output_ids - each generated token's log-probability and the
+    # params.logprobs most likely (token id, log-probability) pairs at its position
+    output_logprobs: List[float] = field(default_factory=list)
+    output_top_logprobs: List[List[Tuple[int, float]]] = field(default_factory=list)
 
     @property
     def all_ids(self) -> List[int]:
@@ -79,6 +83,8 @@ class StepEvent:
     token: int
     finished: bool
     finish_reason: str = ""
+    logprob: Optional[float] = None  # requests with params.logprobs only
+    top_logprobs: Optional[List[Tuple[int, float]]] = None
 
 
 class _DecodeBuffers:
@@ -86,9 +92,10 @@ class _DecodeBuffers:
     per step from one of two pinned staging sets: with decode steps pipelined (LLMEngine.step),
     the host fills step t+1's set while step t's copy may still be queued, so a set is rewritten
     only after the step that used it has been collected. Token ids come back through two pinned
-    output buffers for the same reason."""
+    output buffers for the same reason. ``max_logprobs`` N > 0 adds the log-probability outputs: ``lp_f`` [max_b, 1 + N]
+    fp32 (the sampled token's, then the top N) and ``lp_i`` [max_b, N] int32 (their ids) with two pinned host sets."""
 
-    def __init__(self, max_b: int, max_blocks: int, device):
+    def __init__(self, max_b: int, max_blocks: int, device, max_logprobs: int = 0):
         B, MB = max_b, max_blocks
         self.max_b, self.max_blocks = B, MB
         pin = torch.cuda.is_available() and device.type == "cuda"
@@ -106,6 +113,18 @@ class _DecodeBuffers:
         self.ctx, self.topk = self.d_i32[:B], self.d_i32[B:2 * B]
         self.bt = self.d_i32[2 * B:].view(B, max_blocks)
         self.temp, self.topp = self.d_f32[:B], self.d_f32[B:]
+        N = self.max_logprobs = max_logprobs
+        if N > 0:
+            self.lp_f = torch.zeros(max_b, 1 + N, dtype=torch.float32, device=device)
+            self.lp_i = torch.zeros(max_b, N, dtype=torch.int32, device=device)
+            self.h_lp_f = [torch.zeros(max_b, 1 + N, dtype=torch.float32, pin_memory=pin) for _ in range(2)]
+            self.h_lp_i = [torch.zeros(max_b, N, dtype=torch.int32, pin_memory=pin) for _ in range(2)]
+
+    def lp_out(self, b: int):
+        """The kernels' (lp, top_lp, top_ids) outputs for the first b rows, or None without log-probabilities."""
+        if self.max_logprobs <= 0:
+            return None
+        return self.lp_f[:b, 0], self.lp_f[:b, 1:], self.lp_i[:b]
 
     def fill(self, k, b_pad, ids, pos, slots, seeds, ctx, topk, bt, temp, topp):
         """Stage one step's inputs in set k and copy them to the device. ``ids=None``: the input ids
@@ -142,8 +161,14 @@ class LLMEngine:
                  kv_fraction: float = 0.9, use_graphs: Optional[bool] = None, eos_token_id: Optional[int] = None,
                  graph_buckets: Optional[Sequence[int]] = None, check_tokens: Optional[bool] = None,
                  autotune: Optional[bool] = None, prefill_chunk: Optional[int] = None,
-                 kv_dtype: Optional[str] = None):
+                 kv_dtype: Optional[str] = None, max_logprobs: int = 0):
         self.model = model
+        # launch-time opt-in: N > 0 computes, after every sampler call, the sampled token's log-probability and the
+        # N most likely tokens (ops.token_logprobs); 0 leaves graphs, buffers and steps as they are
+        if not (isinstance(max_logprobs, int) and 0 <= max_logprobs <= MAX_TOP_LOGPROBS):
+            raise ValueError(f"max_logprobs must be an integer in 0..{MAX_TOP_LOGPROBS}, not {max_logprobs!r}")
+        self.max_logprobs = max_logprobs
+        self._step_lps = None  # (values [n, 1 + N], ids [n, N]) of the last eager sampling step, on the host
         if kv_dtype is not None:  # "bf16" (model dtype) or "fp8" (e4m3 rows + per-row scale)
             if kv_dtype not in ("bf16", "fp8"):
                 raise ValueError(f"kv_dtype must be 'bf16' or 'fp8', not {kv_dtype!r}")
@@ -210,7 +235,8 @@ class LLMEngine:
         # (column-chunked all-reduces beside the next chunk's GEMM)
         self.decode_schedule: Dict[int, str] = {}
         self.tp.check_consistent("LLMEngine", self.fingerprint())
-        self.buf = _DecodeBuffers(self.buckets[-1], self.max_blocks, self.device) if self.is_gpu else None
+        self.buf = _DecodeBuffers(self.buckets[-1], self.max_blocks, self.device, self.max_logprobs) \
+            if self.is_gpu else None
         if self.is_gpu:
             _hip_ops.reserve_workspace(self.device, 64 << 20)
             for b in self.decode_batch_sizes():
@@ -264,7 +290,7 @@ class LLMEngine:
                 "max_num_seqs": self.max_num_seqs, "max_batched_tokens": self.max_batched_tokens,
                 "buckets": list(self.buckets), "graphs": bool(self.use_graphs),
                 "async_decode": self.async_decode, "eos": self.eos, "prefill_chunk": self.prefill_chunk, "window": self.window,
-                "dist_sampling": self.dist_sampling, "kv_fp8": bool(self.model.kv_fp8),
+                "dist_sampling": self.dist_sampling, "max_logprobs": self.max_logprobs, "kv_fp8": bool(self.model.kv_fp8),
                 "overlap_rows": self.model.overlap_rows, "bucket_bytes": self.model.bucket_bytes,
                 "tbo_min": self.model.tbo_min, "graph_keys": sorted(self.graphs),
                 "decode_schedule": sorted(self.decode_schedule.items()), "rsag_mode": self.model.rsag_mode,
@@ -409,6 +435,14 @@ class LLMEngine:
     def add_request(self, prompt_ids: Sequence[int], params: Optional[SamplingParams] = None,
                     req_id: Optional[int] = None) -> int:
         params = params or SamplingParams()
+        if params.logprobs is not None:
+            params.validate()
+            if self.max_logprobs == 0:
+                raise ValueError("log-probabilities were requested but the engine was launched without them "
+                                 "(LLMEngine(max_logprobs=N), server --max-logprobs N)")
+            if params.logprobs > self.max_logprobs:
+                raise ValueError(f"logprobs = {params.logprobs} exceeds the engine's max_logprobs = "
+                                 f"{self.max_logprobs}")
         prompt = list(int(t) for t in prompt_ids)
         if not prompt:
             raise ValueError("empty prompt")
@@ -503,7 +537,8 @@ class LLMEngine:
                 self.stats["mixed_decode_tokens"] = self.stats.get("mixed_decode_tokens", 0) + batch.num_decode
                 self.stats["prefill_time_s"] += time.perf_counter() - t0
                 smp = batch.sample
-                new_events = self._emit(*self._apply(ids[smp], [r for r, f in zip(reqs, smp) if f], tokens))
+                new_events = self._emit(*self._apply(ids[smp], [r for r, f in zip(reqs, smp) if f], tokens,
+                                                     self._step_lps))
             elif self.is_gpu:
                 self._launch_decode(self._record_from_batch(batch, ids, reqs))
             else:
@@ -511,7 +546,7 @@ class LLMEngine:
                 tokens = self._decode_cpu(batch, reqs)
                 self.stats["decode_steps"] += 1
                 self.stats["decode_time_s"] += time.perf_counter() - t0
-                new_events = self._emit(*self._apply(ids, reqs, tokens))
+                new_events = self._emit(*self._apply(ids, reqs, tokens, self._step_lps))
         if hp:
             t_d = time.perf_counter()
             self.stats["host_launch_s"] = self.stats.get("host_launch_s", 0.0) + t_d - t_c
@@ -520,12 +555,26 @@ class LLMEngine:
             self.stats["host_emit_s"] = self.stats.get("host_emit_s", 0.0) + time.perf_counter() - t_d
         return events
 
-    def _apply(self, ids: np.ndarray, reqs: List[Request], tokens: List[int]):
-        """Critical-path bookkeeping of one step's tokens: append, stop checks, scheduler update."""
+    def _apply(self, ids: np.ndarray, reqs: List[Request], tokens: List[int], lps=None):
+        """Critical-path bookkeeping of one step's tokens: append, stop checks, scheduler update. ``lps``: the step's
+        log-probability rows (values [n, 1 + N], ids [n, N]) for the same requests; each request that asked keeps
+        its token's and the first params.logprobs alternatives."""
         if self.check_tokens and self.tp.is_real:
             allt = self.tp.all_gather_object(tokens)
             if any(t != tokens for t in allt):
                 raise RuntimeError(f"rank {self.tp.rank}: sampled tokens diverged across TP ranks: {allt}")
+        lpinfo = None
+        if lps is not None:
+            lpinfo = [None] * len(reqs)
+            vals, tids = lps
+            for i, r in enumerate(reqs):
+                n = r.params.logprobs
+                if n is None:
+                    continue
+                top = [(int(t), float(v)) for t, v in zip(tids[i, :n].tolist(), vals[i, 1:1 + n].tolist()) if t >= 0]
+                r.output_logprobs.append(float(vals[i, 0]))
+                r.output_top_logprobs.append(top)
+                lpinfo[i] = (r.output_logprobs[-1], top)
         eos = self.eos
         reasons = [""] * len(reqs)
         fins = np.zeros(len(reqs), dtype=bool)
@@ -545,18 +594,21 @@ class LLMEngine:
         self.sched.on_tokens(ids, fins)
         self._last_fins = fins
         self.stats["steps"] += 1
-        return reqs, tokens, reasons, time.perf_counter()
+        return reqs, tokens, reasons, time.perf_counter(), lpinfo
 
-    def _emit(self, reqs, tokens, reasons, now) -> List[StepEvent]:
+    def _emit(self, reqs, tokens, reasons, now, lpinfo=None) -> List[StepEvent]:
         events = []
-        for r, tok, reason in zip(reqs, tokens, reasons):
+        for i, (r, tok, reason) in enumerate(zip(reqs, tokens, reasons)):
             if not r.t_first:
                 r.t_first = now
             r.t_last = now
             r.token_times.append(now)
             if reason:
                 r.finished, r.finish_reason = True, reason
-            events.append(StepEvent(r.id, tok, bool(reason), reason))
+            ev = StepEvent(r.id, tok, bool(reason), reason)
+            if lpinfo is not None and lpinfo[i] is not None:
+                ev.logprob, ev.top_logprobs = lpinfo[i]
+            events.append(ev)
         self.stats["tokens"] += len(events)
         return events
 
@@ -586,39 +638,60 @@ class LLMEngine:
             ctx_lens=d(ctx.astype(np.int32)) if kind == "extend" else None, max_ctx=self.max_model_len,
             num_decode=nd, has_prefix=has_prefix, cu_host=cu if kind == "prefill" else None, window=self.window)
         reqs = [r for r, f in zip(reqs, smp) if f]
+        self._step_lps = None
         if not reqs:
             self.model.hidden_states(inp, self.kv)  # prompt chunks only: fill the cache, nothing to sample
             return []
         temp, topk, topp, seeds = self._sampling_arrays(reqs)
         tok = self._forward_sample(inp, *(torch.from_numpy(a).to(dev) for a in (temp, topk, topp, seeds)),
                                    dist=self._dist_ok(temp, topk))
+        self._step_lps = self._lps_to_host()
         return tok.cpu().tolist()
 
     def _dist_ok(self, temp, topk) -> bool:
         """Sample this step from vocab-parallel candidates (no [B, V] logits all-gather)?"""
         return self.dist_sampling and ops.cand_ok(temp, topk)
 
-    def _forward_sample(self, inp: StepInput, temp, topk, topp, seeds, out=None, dist=False):
+    def _forward_sample(self, inp: StepInput, temp, topk, topp, seeds, out=None, dist=False, lp_out=None):
         """Forward + LM head + sampler. ``dist``: each rank keeps its logit shard and only candidates
-        are gathered (ops.sample_distributed); otherwise the [B, V] logits are all-gathered."""
+        are gathered (ops.sample_distributed); otherwise the [B, V] logits are all-gathered. With max_logprobs > 0
+        a separate launch after the sampler reads the same logits and the sampled ids (ops.token_logprobs; on the
+        ``dist`` path per-shard packs, an all-gather and a combine) into ``lp_out`` or ``self._lps``."""
         m = self.model
         V = self.cfg.vocab_size
+        N = self.max_logprobs
         if dist:
             h = m.hidden_states(inp, self.kv)
             if inp.last_idx is not None:
                 h = h.index_select(0, inp.last_idx)
-            return ops.sample_distributed(m.local_logits(h), self.tp, m.vocab_lo, V, temp, topk, topp, seeds, out=out)
+            local = m.local_logits(h)
+            tok = ops.sample_distributed(local, self.tp, m.vocab_lo, V, temp, topk, topp, seeds, out=out)
+            if N > 0:
+                self._lps = ops.token_logprobs_distributed(local, self.tp, m.vocab_lo, V, tok, N, out=lp_out)
+            return tok
         logits = m(inp, self.kv)
+        vocab = min(V, logits.shape[-1])
         if logits.is_cuda:
-            return _hip_ops.sample(logits, temp, topk, topp, seeds, vocab=min(V, logits.shape[-1]), out=out)
-        return ops.sample(logits, temp, topk, topp, seeds, vocab=min(V, logits.shape[-1]))
+            tok = _hip_ops.sample(logits, temp, topk, topp, seeds, vocab=vocab, out=out)
+        else:
+            tok = ops.sample(logits, temp, topk, topp, seeds, vocab=vocab)
+        if N > 0:
+            self._lps = ops.token_logprobs(logits, vocab, tok, N, out=lp_out)
+        return tok
+
+    def _lps_to_host(self):
+        """The last eager sampling step's log-probabilities as numpy (values [n, 1 + N], ids [n, N])."""
+        if self.max_logprobs <= 0:
+            return None
+        lp, top, tids = self._lps
+        return torch.cat([lp.view(-1, 1), top], dim=1).cpu().numpy(), tids.cpu().numpy()
 
     def _decode_forward(self, b: int, buf: _DecodeBuffers, dist: bool = False):
         inp = StepInput(kind="decode", input_ids=buf.ids[:b], positions=buf.pos[:b], slots=buf.slots[:b],
                         block_tables=buf.bt[:b], ctx_lens=buf.ctx[:b], max_ctx=self.max_model_len,
                         decode_splits=self._splits(b), window=self.window)
         self._forward_sample(inp, buf.temp[:b], buf.topk[:b], buf.topp[:b], buf.seeds[:b], out=buf.out[:b],
-                             dist=dist)
+                             dist=dist, lp_out=buf.lp_out(b))
 
     def _decode_cpu(self, batch, reqs: List[Request]) -> List[int]:
         ids = np.array([r.last_id for r in reqs], dtype=np.int64)
@@ -628,7 +701,9 @@ class LLMEngine:
                         block_tables=torch.from_numpy(batch.block_table.astype(np.int32)),
                         ctx_lens=torch.from_numpy(batch.ctx_lens.astype(np.int32)), max_ctx=self.max_model_len,
                         window=self.window)
-        return self._forward_sample(inp, temp, topk, topp, seeds, dist=self._dist_ok(temp, topk)).tolist()
+        tok = self._forward_sample(inp, temp, topk, topp, seeds, dist=self._dist_ok(temp, topk))
+        self._step_lps = self._lps_to_host()
+        return tok.tolist()
 
     # ------------------------------------------------------------------ pipelined GPU decode
     def _record_from_batch(self, batch, ids: np.ndarray, reqs: List[Request]) -> dict:
@@ -677,6 +752,9 @@ class LLMEngine:
             if self._host_prof:
                 self.stats["host_replay_s"] = self.stats.get("host_replay_s", 0.0) + time.perf_counter() - t_r
             buf.h_out[k][:n].copy_(buf.out[:n], non_blocking=True)
+            if self.max_logprobs > 0:
+                buf.h_lp_f[k][:n].copy_(buf.lp_f[:n], non_blocking=True)
+                buf.h_lp_i[k][:n].copy_(buf.lp_i[:n], non_blocking=True)
             ev = torch.cuda.Event()
             ev.record()
         rec.update(k=k, ev=ev)
@@ -748,7 +826,11 @@ class LLMEngine:
         now = time.perf_counter()
         self.stats["decode_time_s"] += now - max(rec["t0"], self._t_collect)
         self._t_collect = now
-        out = self._apply(ids, sel, tokens)
+        lps = None
+        if self.max_logprobs > 0:  # kept rows only: a speculated step's dropped token drops its log-probability too
+            k, n = rec["k"], rec["n"]
+            lps = (self.buf.h_lp_f[k][:n].numpy()[rows], self.buf.h_lp_i[k][:n].numpy()[rows])
+        out = self._apply(ids, sel, tokens, lps)
         fins = self._last_fins
         nxt = self._pending[0] if self._pending else None
         if nxt is not None:  # the speculated successor drops rows that stopped (eos / stop / abort) here

@@ -24,6 +24,7 @@ import numpy as np
 
 _seed_counter = itertools.count(int.from_bytes(os.urandom(4), "little"))
 MASK64 = (1 << 64) - 1
+MAX_TOP_LOGPROBS = 20  # most alternatives per generated position a request may ask for (csrc/logprobs.hip)
 
 
 @dataclass
@@ -36,6 +37,11 @@ class SamplingParams:
     seed: Optional[int] = None
     stop_token_ids: List[int] = field(default_factory=list)
     ignore_eos: bool = False
+    # log-probabilities of the raw model distribution log_softmax(logits[:vocab]) - temperature, top-k and top-p are
+    # not applied. None: none returned; 0: each generated token's; n in 1..MAX_TOP_LOGPROBS: additionally the n most
+    # likely tokens at each generated position (logit descending, ties by ascending id). Needs an engine launched
+    # with max_logprobs >= n.
+    logprobs: Optional[int] = None
 
     def validate(self) -> "SamplingParams":
         """Reference validation (generate.py:37-40)."""
@@ -47,6 +53,9 @@ class SamplingParams:
             raise ValueError("Value of top_p is not valid.")
         if not self.top_k >= 0:
             raise ValueError("Value of top_k is not valid.")
+        lp = self.logprobs
+        if lp is not None and not (isinstance(lp, int) and not isinstance(lp, bool) and 0 <= lp <= MAX_TOP_LOGPROBS):
+            raise ValueError(f"Value of logprobs should be None or an integer in 0..{MAX_TOP_LOGPROBS}.")
         return self
 
     def resolved_seed(self) -> int:

@@ -13,7 +13,8 @@ import torch
 from . import reference as ref
 
 __all__ = ["add_norm", "embed", "rope_cache", "attn_prefill", "attn_decode", "attn_extend", "linear", "sample", "quant_fp8_rows",
-           "rope_tables", "glu_interleave", "glu_split", "cross_entropy"]
+           "rope_tables", "glu_interleave", "glu_split", "cross_entropy", "token_logprobs",
+           "token_logprobs_distributed", "MAX_TOP_LOGPROBS"]
 
 rope_tables = ref.rope_tables
 glu_interleave = ref.glu_interleave
@@ -149,6 +150,42 @@ def sample_distributed(local, tp, lo, V, temperature, top_k, top_p, seeds, out=N
     allp = tp.all_gather_last_dim(pack)
     y = ref.sample_cand(allp, allp.shape[1] // (2 * CAND_KC), CAND_KC, temperature, top_k, top_p, seeds, V)
     return _into(y, out)
+
+
+MAX_TOP_LOGPROBS = ref.MAX_TOP_LOGPROBS
+
+
+def _lp_out(res, out):
+    if out is None:
+        return res
+    for o, r in zip(out, res):
+        o.copy_(r)
+    return out
+
+
+def token_logprobs(logits, V, tokens, N, out=None):
+    """Log-probabilities of the raw model distribution ``log_softmax(logits[:, :V])`` (natural log; no temperature,
+    top-k or top-p): of ``tokens`` [B] int64, and of the N (0..MAX_TOP_LOGPROBS) most likely tokens per row ordered
+    by logit descending, ties by ascending id. Returns (lp [B] fp32, top_lp [B, N] fp32, top_ids [B, N] int32);
+    where N > V the entries past V are -inf / -1. ``out``: the three tensors to write into."""
+    if logits.is_cuda:
+        return _hip().token_logprobs(logits, V, tokens, N, out=out)
+    if not (isinstance(N, int) and 0 <= N <= MAX_TOP_LOGPROBS):
+        raise ValueError(f"N must be an int in 0..{MAX_TOP_LOGPROBS}, got {N!r}")
+    return _lp_out(ref.token_logprobs(logits, V, tokens, N), out)
+
+
+def token_logprobs_distributed(local, tp, lo, V, tokens, N, out=None, shards=1):
+    """``token_logprobs`` over a vocab-parallel head without gathering logits: per-shard (max, sum, token logit,
+    top N) packs -> all-gather -> combine. Every rank returns the same bits."""
+    if not (isinstance(N, int) and 0 <= N <= MAX_TOP_LOGPROBS):
+        raise ValueError(f"N must be an int in 0..{MAX_TOP_LOGPROBS}, got {N!r}")
+    if local.is_cuda:
+        h = _hip()
+        allp = tp.all_gather_last_dim(h.token_logprobs_partial(local, lo, V, tokens, N, shards=shards))
+        return h.token_logprobs_combine(allp, N, out=out)
+    allp = tp.all_gather_last_dim(ref.token_logprobs_partial(local, lo, V, tokens, N, shards=shards))
+    return _lp_out(ref.token_logprobs_combine(allp, N), out)
 
 
 def quant_fp8_rows(w):

@@ -802,3 +802,85 @@ def sample(logits, temperature, top_k, top_p, seeds, vocab: Optional[int] = None
     lib().sample(logits.data_ptr(), logits.stride(0), logits.dtype == torch.float32, B, V, _ptr(temperature),
                  _ptr(top_k), _ptr(top_p), _ptr(seeds), y.data_ptr(), _ptr(out2), _stream())
     return y
+
+
+# -------------------------------------------------------------------------------- log-probabilities
+MAX_TOP_LOGPROBS = _ref.MAX_TOP_LOGPROBS
+LOGPROB_MAX_CAND = 2048  # groups * N the combine kernel ranks in LDS
+
+
+def _lp_logits(logits, tokens, N, name="logits"):
+    _check(isinstance(N, int) and 0 <= N <= MAX_TOP_LOGPROBS, f"N must be an int in 0..{MAX_TOP_LOGPROBS}, got {N!r}")
+    _check(logits.is_cuda and logits.dim() == 2 and logits.stride(1) == 1, f"{name} must be [B, V] GPU rows")
+    _check(logits.device.index == torch.cuda.current_device(),
+           f"{name} is on {logits.device} but the current device is cuda:{torch.cuda.current_device()}")
+    _check(logits.dtype in (torch.bfloat16, torch.float32), f"{name} must be bfloat16 or float32, got {logits.dtype}")
+    _check(logits.shape[0] == 0 or logits.stride(0) >= logits.shape[1], f"{name} rows overlap")
+    B = logits.shape[0]
+    _check(torch.is_tensor(tokens) and tokens.dtype == torch.int64 and tokens.device == logits.device
+           and tokens.dim() == 1 and tokens.shape[0] == B and tokens.is_contiguous(),
+           f"tokens must be a contiguous int64 [B={B}] tensor on {logits.device}")
+    return B
+
+
+def _lp_outputs(B, N, device, out):
+    """(lp [B], top_lp [B, N], top_ids [B, N]): fresh, or the caller's (row-strided views are fine)."""
+    if out is None:
+        return (torch.empty(B, dtype=torch.float32, device=device),
+                torch.empty(B, N, dtype=torch.float32, device=device),
+                torch.empty(B, N, dtype=torch.int32, device=device))
+    lp, top, ids = out
+    for t, dt, shape, nm in ((lp, torch.float32, (B,), "lp"), (top, torch.float32, (B, N), "top_lp"),
+                             (ids, torch.int32, (B, N), "top_ids")):
+        _check(t.dtype == dt and tuple(t.shape) == shape and t.device == device, f"out {nm} must be {dt} {shape}")
+        _check(t.dim() == 1 or N == 0 or t.stride(1) == 1, f"out {nm} rows must be contiguous")
+        _check(B <= 1 or t.stride(0) >= (1 if t.dim() == 1 else N), f"out {nm} rows overlap")
+    return lp, top, ids
+
+
+def token_logprobs(logits, V, tokens, N, out=None):
+    """``log_softmax(logits[:, :V])`` of ``tokens`` [B] and of the N most likely tokens per row (logit descending,
+    ties by ascending id): (lp [B] fp32, top_lp [B, N] fp32, top_ids [B, N] int32); entries past V are -inf / -1."""
+    B = _lp_logits(logits, tokens, N)
+    V = int(V)
+    _check(1 <= V <= logits.shape[1], f"V = {V} outside the logits row of {logits.shape[1]} columns")
+    lp, top, ids = _lp_outputs(B, N, logits.device, out)
+    lib().token_logprobs(logits.data_ptr(), logits.stride(0), logits.dtype == torch.float32, B, V, 0, V,
+                         tokens.data_ptr(), N, 1, lp.data_ptr(), lp.stride(0) if B else 1, top.data_ptr(),
+                         top.stride(0), ids.data_ptr(), ids.stride(0), 0, 0, _stream())
+    return lp, top, ids
+
+
+def token_logprobs_partial(local, lo, V, tokens, N, shards=1, out=None):
+    """Packs of a vocab-parallel shard ``local`` [B, width] whose column 0 is global token ``lo``:
+    [B, shards * (3 + 2N)] fp32 (ops/reference.py token_logprobs_partial). ``shards`` > 1 cuts the row into that
+    many column shards in one launch, packed shard-major like gathered per-rank packs."""
+    B = _lp_logits(local, tokens, N, "local logits")
+    _check(isinstance(shards, int) and shards >= 1, "shards must be a positive int")
+    _check(int(lo) >= 0 and int(V) >= 1, "lo / V")
+    width = local.shape[1]
+    _check(width >= 1, "empty shard")
+    P = 3 + 2 * N
+    pack = out if out is not None else torch.empty(B, shards * P, dtype=torch.float32, device=local.device)
+    _check(pack.dtype == torch.float32 and tuple(pack.shape) == (B, shards * P) and pack.device == local.device
+           and pack.stride(1) == 1 and (B <= 1 or pack.stride(0) >= shards * P), "log-probability pack")
+    lib().token_logprobs(local.data_ptr(), local.stride(0), local.dtype == torch.float32, B, width, int(lo), int(V),
+                         tokens.data_ptr(), N, shards, 0, 0, 0, 0, 0, 0, pack.data_ptr(), pack.stride(0), _stream())
+    return pack
+
+
+def token_logprobs_combine(pack, N, out=None):
+    """Merge gathered packs [B, groups * (3 + 2N)] (rank-major) into (lp, top_lp, top_ids)."""
+    _check(isinstance(N, int) and 0 <= N <= MAX_TOP_LOGPROBS, f"N must be an int in 0..{MAX_TOP_LOGPROBS}")
+    _check(pack.is_cuda and pack.dtype == torch.float32 and pack.dim() == 2 and pack.stride(1) == 1, "pack")
+    _check(pack.device.index == torch.cuda.current_device(), "pack is not on the current device")
+    B = pack.shape[0]
+    P = 3 + 2 * N
+    _check(pack.shape[1] >= P and pack.shape[1] % P == 0, f"pack width must be a multiple of 3 + 2N = {P}")
+    _check(B <= 1 or pack.stride(0) >= pack.shape[1], "pack rows overlap")
+    groups = pack.shape[1] // P
+    _check(groups * N <= LOGPROB_MAX_CAND, "too many gathered candidates per row")
+    lp, top, ids = _lp_outputs(B, N, pack.device, out)
+    lib().logprobs_combine(pack.data_ptr(), pack.stride(0), B, groups, N, lp.data_ptr(), lp.stride(0) if B else 1,
+                           top.data_ptr(), top.stride(0), ids.data_ptr(), ids.stride(0), _stream())
+    return lp, top, ids

@@ -473,6 +473,103 @@ def sample_cand(pack: torch.Tensor, groups: int, KC: int, temperature, top_k, to
     return out.to(pack.device)
 
 
+MAX_TOP_LOGPROBS = 20
+
+
+def _top_order(x: torch.Tensor, ids: torch.Tensor, N: int):
+    """The first N of ``x`` [B, n] by (value descending, id ascending) with their ``ids`` [n] (ascending):
+    (values [B, N] fp32, ids [B, N] int32), -inf / -1 past n. A stable sort keeps equal values in id order;
+    ``torch.topk`` leaves the order of ties undefined."""
+    B, n = x.shape
+    vals = torch.full((B, N), float("-inf"), dtype=torch.float32, device=x.device)
+    out = torch.full((B, N), -1, dtype=torch.int32, device=x.device)
+    k = min(N, n)
+    if k:
+        order = torch.sort(x, dim=1, descending=True, stable=True).indices[:, :k]
+        vals[:, :k] = x.gather(1, order)
+        out[:, :k] = ids[order].to(torch.int32)
+    return vals, out
+
+
+def token_logprobs(logits: torch.Tensor, V: int, tokens: torch.Tensor, N: int):
+    """Log-probabilities of the raw model distribution (GPU ``token_logprobs``): ``log_softmax(logits[:, :V])``
+    of ``tokens`` [B] and of the N most likely tokens per row, logit descending and ties by ascending id.
+    Returns (lp [B] fp32, top_lp [B, N] fp32, top_ids [B, N] int32)."""
+    x = logits[:, :V].float()
+    # max / sum exp / log spelled out: torch.sum adds in a cascade, while log_softmax's own row sum is one serial
+    # chain per vector lane, whose rounding on a row of thousands of equal terms exceeds the kernels' bound
+    m = x.max(dim=-1, keepdim=True).values
+    lsm = x - (m + torch.log(torch.exp(x - m).sum(dim=-1, keepdim=True)))
+    lp = lsm.gather(1, tokens.view(-1, 1).long()).squeeze(1)
+    _, ids = _top_order(x, torch.arange(V, device=x.device), N)
+    top = torch.full(ids.shape, float("-inf"), dtype=torch.float32, device=x.device)
+    k = min(N, V)
+    if k:
+        top[:, :k] = lsm.gather(1, ids[:, :k].long())
+    return lp, top, ids
+
+
+def token_logprobs_partial(local: torch.Tensor, lo: int, V: int, tokens: torch.Tensor, N: int,
+                           shards: int = 1) -> torch.Tensor:
+    """Per-shard packs of a vocab-parallel logit shard whose column 0 is global token ``lo`` (GPU partial mode):
+    [B, shards * (3 + 2N)] fp32, per shard [max, sum exp(x - max), raw logit of the token or -inf, N raw logits,
+    N global ids as int32 bits]."""
+    B, width = local.shape
+    vl = -(-width // shards)
+    P = 3 + 2 * N
+    pack = torch.empty(B, shards * P, dtype=torch.float32, device=local.device)
+    tok = tokens.view(-1).long()
+    for s in range(shards):
+        c0 = s * vl
+        n = max(0, min(vl, width - c0, V - (lo + c0)))
+        x = local[:, c0:c0 + n].float()
+        p = pack[:, s * P:(s + 1) * P]
+        if n:
+            m = x.max(dim=1).values
+            p[:, 0] = m
+            p[:, 1] = torch.exp(x - m[:, None]).sum(dim=1)
+            j = tok - (lo + c0)
+            inside = (j >= 0) & (j < n)
+            xt = x.gather(1, j.clamp(0, n - 1).view(-1, 1)).squeeze(1)
+            p[:, 2] = torch.where(inside, xt, torch.full_like(xt, float("-inf")))
+        else:
+            p[:, 0] = float("-inf")
+            p[:, 1] = 0.0
+            p[:, 2] = float("-inf")
+        vals, ids = _top_order(x, torch.arange(lo + c0, lo + c0 + n, device=local.device), N)
+        p[:, 3:3 + N] = vals
+        p[:, 3 + N:] = ids.view(torch.float32)
+    return pack
+
+
+def token_logprobs_combine(pack: torch.Tensor, N: int):
+    """Merge gathered packs [B, groups * (3 + 2N)] (GPU ``logprobs_combine``): M = max m_r, S = sum_r s_r exp(m_r - M)
+    in rank order, lp = x_tok - M - log S, and the groups' candidates merged by (value desc, id asc)."""
+    B = pack.shape[0]
+    P = 3 + 2 * N
+    g = pack.view(B, -1, P)
+    G = g.shape[1]
+    M = g[:, :, 0].max(dim=1).values
+    S = torch.zeros(B, dtype=torch.float32, device=pack.device)
+    for r in range(G):
+        S = S + g[:, r, 1] * torch.exp(g[:, r, 0] - M)
+    lse = M + torch.log(S)
+    lp = g[:, :, 2].max(dim=1).values - lse
+    vals = g[:, :, 3:3 + N].reshape(B, G * N)
+    ids = g[:, :, 3 + N:].contiguous().view(torch.int32).reshape(B, G * N)
+    top = torch.full((B, N), float("-inf"), dtype=torch.float32, device=pack.device)
+    tid = torch.full((B, N), -1, dtype=torch.int32, device=pack.device)
+    for b in range(B):
+        keep = ids[b] >= 0
+        v, i = vals[b][keep], ids[b][keep]
+        o = torch.sort(i, stable=True).indices  # id ascending, then a stable sort by value
+        v, i = v[o], i[o]
+        o = torch.sort(v, descending=True, stable=True).indices[:N]
+        top[b, :o.numel()] = v[o] - lse[b]
+        tid[b, :o.numel()] = i[o]
+    return lp, top, tid
+
+
 def cross_entropy(logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
     """Shifted LM loss as in the reference (gptj_modeling.py:612-622)."""
     return F.cross_entropy(logits[..., :-1, :].reshape(-1, logits.shape[-1]).float(),

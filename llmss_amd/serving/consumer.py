@@ -137,6 +137,9 @@ class Consumer:
                         finish_reason=h.finish_reason, ttft_s=m.get("ttft_s"), e2e_s=m.get("e2e_s"))
             if req.stream:
                 resp.update(finished=True, text="")
+        if h.params.logprobs is not None:
+            resp.update(token_logprobs=list(h.output_logprobs),
+                        top_logprobs=[[[i, v] for i, v in top] for top in h.output_top_logprobs])
         if h.finish_reason == "error":
             resp["error"] = h.error or "engine failure"
         self.served += 1

@@ -56,6 +56,10 @@ class Handle:
     tokens: "queue.Queue[Optional[int]]" = field(default_factory=queue.Queue)
     done: threading.Event = field(default_factory=threading.Event)
     output_ids: List[int] = field(default_factory=list)
+    # params.logprobs is not None: parallel to output_ids (engine Request.output_logprobs / output_top_logprobs); an
+    # entry is appended BEFORE its token reaches tokens / on_token / the sink, so a consumer finds it there
+    output_logprobs: List[float] = field(default_factory=list)
+    output_top_logprobs: List[list] = field(default_factory=list)
     finish_reason: str = ""
     metrics: Dict[str, float] = field(default_factory=dict)
     on_done: Optional[Callable[["Handle"], None]] = None
@@ -438,6 +442,9 @@ class EngineDriver:
                         h = self.handles.get(ev.req_id)
                         if h is None:
                             continue
+                        if ev.logprob is not None:
+                            h.output_logprobs.append(ev.logprob)
+                            h.output_top_logprobs.append(ev.top_logprobs)
                         h.output_ids.append(ev.token)
                         if h.stream:
                             h.tokens.put(ev.token)

@@ -42,16 +42,22 @@ def _build_pool():
     def msg(name, fields):
         m = fd.message_type.add(name=name)
         for num, (fname, ftype, rep) in enumerate(fields, 1):
-            m.field.add(name=fname, number=num, type=ftype,
-                        label=_F.LABEL_REPEATED if rep else _F.LABEL_OPTIONAL)
+            f = m.field.add(name=fname, number=num, type=_F.TYPE_MESSAGE if isinstance(ftype, str) else ftype,
+                            label=_F.LABEL_REPEATED if rep else _F.LABEL_OPTIONAL)
+            if isinstance(ftype, str):  # a message of this package
+                f.type_name = f".llmss.{ftype}"
 
     S, I32, I64, B, FL = _F.TYPE_STRING, _F.TYPE_INT32, _F.TYPE_INT64, _F.TYPE_BOOL, _F.TYPE_FLOAT
     msg("GenerateRequest", [("prompt", S, 0), ("max_new_tokens", I32, 0), ("is_greedy", B, 0), ("temperature", FL, 0),
                             ("top_p", FL, 0), ("top_k", I32, 0), ("request_id", S, 0), ("seed", I64, 0),
-                            ("prompt_token_ids", I32, 1), ("ignore_eos", B, 0)])
+                            ("prompt_token_ids", I32, 1), ("ignore_eos", B, 0), ("return_logprobs", B, 0),
+                            ("top_logprobs", I32, 0)])
+    msg("TopLogprobs", [("token_ids", I32, 1), ("logprobs", FL, 1)])
     msg("GenerateResponse", [("prompt", S, 0), ("continuation", S, 0), ("request_id", S, 0), ("token_ids", I32, 1),
-                             ("finish_reason", S, 0), ("ttft_s", FL, 0), ("e2e_s", FL, 0)])
-    msg("Token", [("token_id", I32, 0), ("text", S, 0), ("finished", B, 0), ("finish_reason", S, 0)])
+                             ("finish_reason", S, 0), ("ttft_s", FL, 0), ("e2e_s", FL, 0), ("token_logprobs", FL, 1),
+                             ("top_logprobs", "TopLogprobs", 1)])
+    msg("Token", [("token_id", I32, 0), ("text", S, 0), ("finished", B, 0), ("finish_reason", S, 0),
+                  ("logprob", FL, 0), ("top", "TopLogprobs", 0)])
     msg("StatsRequest", [])
     msg("StatsResponse", [("json", S, 0)])
     svc = fd.service.add(name="Generate")
@@ -68,20 +74,43 @@ _POOL = _build_pool()
 GenerateRequest = message_factory.GetMessageClass(_POOL.FindMessageTypeByName("llmss.GenerateRequest"))
 GenerateResponse = message_factory.GetMessageClass(_POOL.FindMessageTypeByName("llmss.GenerateResponse"))
 Token = message_factory.GetMessageClass(_POOL.FindMessageTypeByName("llmss.Token"))
+TopLogprobs = message_factory.GetMessageClass(_POOL.FindMessageTypeByName("llmss.TopLogprobs"))
 StatsRequest = message_factory.GetMessageClass(_POOL.FindMessageTypeByName("llmss.StatsRequest"))
 StatsResponse = message_factory.GetMessageClass(_POOL.FindMessageTypeByName("llmss.StatsResponse"))
 
 SERVICE = "llmss.Generate"
 
 
-def _params(req):
+def _top_msg(top):
+    """[(token id, log-probability), ...] -> TopLogprobs."""
+    return TopLogprobs(token_ids=[i for i, _ in top], logprobs=[v for _, v in top])
+
+
+def _logprob_fields(token_logprobs, top_logprobs) -> dict:
+    """GenerateResponse fields of a reply's log-probabilities (none when the request did not ask)."""
+    if token_logprobs is None:
+        return {}
+    return {"token_logprobs": token_logprobs,
+            "top_logprobs": [_top_msg([tuple(p) for p in t]) for t in top_logprobs or []]}
+
+
+def _params(req, max_logprobs: Optional[int] = None):
+    """``max_logprobs``: the serving engine's launch-time limit when known - a log-probability request it cannot
+    serve is a ValueError here (INVALID_ARGUMENT), not a failed handle later."""
     from ..engine.sampling import SamplingParams
+
+    logprobs = int(req.top_logprobs) if req.return_logprobs else None
+    if logprobs is not None and max_logprobs is not None:
+        if max_logprobs == 0:
+            raise ValueError("log-probabilities are not enabled on this server (--max-logprobs N)")
+        if logprobs > max_logprobs:
+            raise ValueError(f"top_logprobs = {logprobs} exceeds the server's --max-logprobs {max_logprobs}")
 
     # proto3 scalars default to 0: 0 means "reference default" for max_new_tokens/temperature/top_p
     # (0 is invalid for them) and "disabled" for top_k (as in the reference CLI, generate.py:30).
     return SamplingParams(max_new_tokens=req.max_new_tokens or 20, is_greedy=req.is_greedy,
                           temperature=req.temperature or 1.0, top_p=req.top_p or 0.95, top_k=req.top_k,
-                          seed=req.seed or None, ignore_eos=req.ignore_eos).validate()
+                          seed=req.seed or None, ignore_eos=req.ignore_eos, logprobs=logprobs).validate()
 
 
 def add_servicer(server: grpc.Server, servicer) -> None:
@@ -261,6 +290,9 @@ class EngineServicer:
         self.tok = tokenizer
         self._sinks = {}  # event loop -> _LoopSink
 
+    def _max_logprobs(self):
+        return getattr(getattr(self.driver, "engine", None), "max_logprobs", None)
+
     def _prompt_ids(self, req):
         from ..utils.tokenizer import encode
 
@@ -270,7 +302,7 @@ class EngineServicer:
 
     async def Generate(self, req, ctx):
         try:
-            params = _params(req)
+            params = _params(req, self._max_logprobs())
         except ValueError as e:
             await ctx.abort(grpc.StatusCode.INVALID_ARGUMENT, str(e))
         loop = asyncio.get_running_loop()
@@ -293,11 +325,13 @@ class EngineServicer:
         m = h.metrics or {}
         return GenerateResponse(prompt=req.prompt, continuation=self.tok.decode(h.output_ids), request_id=req.request_id,
                                 token_ids=h.output_ids, finish_reason=h.finish_reason,
-                                ttft_s=float(m.get("ttft_s", 0.0) or 0.0), e2e_s=float(m.get("e2e_s", 0.0) or 0.0))
+                                ttft_s=float(m.get("ttft_s", 0.0) or 0.0), e2e_s=float(m.get("e2e_s", 0.0) or 0.0),
+                                **_logprob_fields(h.output_logprobs if params.logprobs is not None else None,
+                                                  h.output_top_logprobs))
 
     async def GenerateStream(self, req, ctx):
         try:
-            params = _params(req)
+            params = _params(req, self._max_logprobs())
         except ValueError as e:
             await ctx.abort(grpc.StatusCode.INVALID_ARGUMENT, str(e))
         loop = asyncio.get_running_loop()
@@ -310,12 +344,18 @@ class EngineServicer:
         from ..utils.tokenizer import StreamDecoder
 
         dec = StreamDecoder(self.tok)  # one short-window decode per token, not the whole prefix again
+        sent = 0
         try:
             while True:
                 t = await q.get()
                 if t is None:
                     break
-                yield Token(token_id=t, text=dec.push(t), finished=False)
+                if params.logprobs is not None:  # the driver appended this token's entry before handing it out
+                    yield Token(token_id=t, text=dec.push(t), finished=False, logprob=h.output_logprobs[sent],
+                                top=_top_msg(h.output_top_logprobs[sent]))
+                else:
+                    yield Token(token_id=t, text=dec.push(t), finished=False)
+                sent += 1
         except asyncio.CancelledError:
             if not h.done.is_set():
                 self.driver.abort(h.rid)
@@ -350,6 +390,7 @@ class BrokerServicer:
         return Request(prompt=req.prompt, max_new_tokens=req.max_new_tokens or 20, is_greedy=req.is_greedy,
                        temperature=req.temperature or 1.0, top_p=req.top_p or 0.95, top_k=req.top_k or 50,
                        request_id=rid, seed=req.seed or None, ignore_eos=req.ignore_eos, stream=stream,
+                       logprobs=int(req.top_logprobs) if req.return_logprobs else None,
                        prompt_token_ids=list(req.prompt_token_ids) or None, deadline_s=deadline_s)
 
     def Generate(self, req, ctx):
@@ -371,7 +412,8 @@ class BrokerServicer:
             ctx.abort(grpc.StatusCode.DEADLINE_EXCEEDED, "generation deadline exceeded")
         return GenerateResponse(prompt=d.get("prompt", ""), continuation=d.get("continuation", ""), request_id=rid,
                                 token_ids=d.get("token_ids") or [], finish_reason=d.get("finish_reason", ""), ttft_s=float(d.get("ttft_s") or 0.0),
-                                e2e_s=float(time.perf_counter() - t0))
+                                e2e_s=float(time.perf_counter() - t0),
+                                **_logprob_fields(d.get("token_logprobs"), d.get("top_logprobs")))
 
     def GenerateStream(self, req, ctx):
         """Streams through the broker: the consumer pushes the tokens of every engine step to the
@@ -438,7 +480,8 @@ class AioBrokerServicer(BrokerServicer):
             await ctx.abort(grpc.StatusCode.DEADLINE_EXCEEDED, "generation deadline exceeded")
         return GenerateResponse(prompt=d.get("prompt", ""), continuation=d.get("continuation", ""), request_id=rid,
                                 token_ids=d.get("token_ids") or [], finish_reason=d.get("finish_reason", ""),
-                                ttft_s=float(d.get("ttft_s") or 0.0), e2e_s=float(time.perf_counter() - t0))
+                                ttft_s=float(d.get("ttft_s") or 0.0), e2e_s=float(time.perf_counter() - t0),
+                                **_logprob_fields(d.get("token_logprobs"), d.get("top_logprobs")))
 
     async def GenerateStream(self, req, ctx):
         from .broker import PQUEUE, reply_key

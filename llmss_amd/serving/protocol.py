@@ -31,6 +31,9 @@ class Request(BaseModel):
     stream: bool = False  # reply per engine step on squeue:<request_id>, then a final "finished" message
     prompt_token_ids: Optional[List[int]] = None  # pre-tokenized prompt (prompt text ignored)
     deadline_s: Optional[float] = None  # seconds the caller waits for the reply: the consumer stops generating then
+    # log-probabilities of the raw model distribution: None none, 0 each generated token's, n also the n most likely
+    # tokens per position (SamplingParams.logprobs; the serving engine needs --max-logprobs >= n)
+    logprobs: Optional[int] = None
 
 
 class Response(BaseModel):
@@ -41,6 +44,11 @@ class Response(BaseModel):
     ttft_s: Optional[float] = None
     e2e_s: Optional[float] = None
     finish_reason: Optional[str] = None
+    # requests with logprobs only (final reply; the broker reply omits them otherwise, like every None): one entry
+    # per generated token, the alternatives as [token id, log-probability] pairs, logit descending and ties by
+    # ascending id
+    token_logprobs: Optional[List[float]] = None
+    top_logprobs: Optional[List[List[List[float]]]] = None
 
 
 def new_request_id() -> str:
@@ -55,7 +63,8 @@ def parse_request(msg: str) -> Request:
 
 def to_sampling(req: Request) -> SamplingParams:
     return SamplingParams(max_new_tokens=req.max_new_tokens, is_greedy=req.is_greedy, temperature=req.temperature,
-                          top_p=req.top_p, top_k=req.top_k, seed=req.seed, ignore_eos=req.ignore_eos).validate()
+                          top_p=req.top_p, top_k=req.top_k, seed=req.seed, ignore_eos=req.ignore_eos,
+                          logprobs=req.logprobs).validate()
 
 
 def dump_response(resp: Dict[str, Any]) -> str:
