@@ -47,10 +47,13 @@ void launch_attn_extend(const void* q, int64_t q_stride, const void* k_cache, co
 int launch_gemm_qkv_args(const void* x, int64_t ldx, const void* w, int64_t ldw, const void* bias, void* y, int64_t ldy,
                          int M, int N, int K, void* workspace, int64_t ws_bytes, int nt_hint, int split_hint,
                          const void* pos, const void* cos_t, const void* sin_t, void* kc, void* vc, const void* slot,
-                         int nh, int nkv, int D, int rot, int block_size, int style, bool do_rope, hipStream_t st);
+                         int nh, int nkv, int D, int rot, int block_size, int style, bool do_rope, hipStream_t st,
+                         const void* w_packed);
 int launch_gemm(const void* x, int64_t ldx, const void* w, int64_t ldw, bool w_fp8, const void* w_scale,
                 const void* bias, void* y, int64_t ldy, int M, int N, int K, int act, bool glu, void* workspace,
-                int64_t ws_bytes, int nt_hint, int split_hint, bool partial_out, hipStream_t st);
+                int64_t ws_bytes, int nt_hint, int split_hint, bool partial_out, hipStream_t st,
+                const void* w_packed);
+void launch_pack_panels(const void* w, int64_t ld, void* p, int64_t N, int64_t K, hipStream_t st);
 void gemm_plan(int M, int N, int K, bool w_fp8, int* nt, int* splitk);
 void gemm_tuned_set(int M, int N, int K, bool glu, int kind, int nt_hint, int split);
 void gemm_tuned_clear();
@@ -155,23 +158,31 @@ PYBIND11_MODULE(_C, m) {
      pybind11::arg("s8") = 0, pybind11::arg("window") = 0, pybind11::arg("kv_starts") = 0);
   m.def("gemm", [](uintptr_t x, int64_t ldx, uintptr_t w, int64_t ldw, bool fp8, uintptr_t ws, uintptr_t bias,
                    uintptr_t y, int64_t ldy, int M, int N, int K, int act, bool glu, uintptr_t work, int64_t wbytes,
-                   int nt_hint, int split_hint, bool partial_out, uintptr_t st) {
+                   int nt_hint, int split_hint, bool partial_out, uintptr_t st, uintptr_t w_packed) {
     return launch_gemm(CP(x), ldx, CP(w), ldw, fp8, CP(ws), CP(bias), P(y), ldy, M, N, K, act, glu, P(work), wbytes,
-                       nt_hint, split_hint, partial_out, S(st));
+                       nt_hint, split_hint, partial_out, S(st), CP(w_packed));
+  }, pybind11::arg("x"), pybind11::arg("ldx"), pybind11::arg("w"), pybind11::arg("ldw"), pybind11::arg("fp8"),
+     pybind11::arg("ws"), pybind11::arg("bias"), pybind11::arg("y"), pybind11::arg("ldy"), pybind11::arg("M"),
+     pybind11::arg("N"), pybind11::arg("K"), pybind11::arg("act"), pybind11::arg("glu"), pybind11::arg("work"),
+     pybind11::arg("wbytes"), pybind11::arg("nt_hint"), pybind11::arg("split_hint"), pybind11::arg("partial_out"),
+     pybind11::arg("st"), pybind11::arg("w_packed") = 0);  // w_packed: the panel-packed copy of w (hint bit 2048)
+  m.def("pack_panels", [](uintptr_t w, int64_t ld, uintptr_t p, int64_t N, int64_t K, uintptr_t st) {
+    launch_pack_panels(CP(w), ld, P(p), N, K, S(st));
   });
   m.def("gemm_qkv", [](uintptr_t x, int64_t ldx, uintptr_t w, int64_t ldw, uintptr_t bias, uintptr_t y, int64_t ldy,
                        int M, int N, int K, uintptr_t work, int64_t wbytes, int nt_hint, int split_hint, uintptr_t pos,
                        uintptr_t cos_t, uintptr_t sin_t, uintptr_t kc, uintptr_t vc, uintptr_t slot, int nh, int nkv,
-                       int D, int rot, int bs, int style, bool do_rope, uintptr_t st) {
+                       int D, int rot, int bs, int style, bool do_rope, uintptr_t st, uintptr_t w_packed) {
     return launch_gemm_qkv_args(CP(x), ldx, CP(w), ldw, CP(bias), P(y), ldy, M, N, K, P(work), wbytes, nt_hint,
                                 split_hint, CP(pos), CP(cos_t), CP(sin_t), P(kc), P(vc), CP(slot), nh, nkv, D, rot, bs,
-                                style, do_rope, S(st));
+                                style, do_rope, S(st), CP(w_packed));
   }, pybind11::arg("x"), pybind11::arg("ldx"), pybind11::arg("w"), pybind11::arg("ldw"), pybind11::arg("bias"),
      pybind11::arg("y"), pybind11::arg("ldy"), pybind11::arg("M"), pybind11::arg("N"), pybind11::arg("K"),
      pybind11::arg("work"), pybind11::arg("wbytes"), pybind11::arg("nt_hint"), pybind11::arg("split_hint"),
      pybind11::arg("pos"), pybind11::arg("cos_t"), pybind11::arg("sin_t"), pybind11::arg("kc"), pybind11::arg("vc"),
      pybind11::arg("slot"), pybind11::arg("nh"), pybind11::arg("nkv"), pybind11::arg("D"), pybind11::arg("rot"),
-     pybind11::arg("bs"), pybind11::arg("style"), pybind11::arg("do_rope"), pybind11::arg("st"));
+     pybind11::arg("bs"), pybind11::arg("style"), pybind11::arg("do_rope"), pybind11::arg("st"),
+     pybind11::arg("w_packed") = 0);
   m.def("gemm_plan", [](int M, int N, int K, bool fp8) {
     int nt, s;
     gemm_plan(M, N, K, fp8, &nt, &s);

@@ -1370,7 +1370,7 @@ __global__ __launch_bounds__(256) void gemm_f8f8_kernel(const unsigned char* __r
 // depth code (2 / 3 / 4 / 4 stages per wave), split_hint = K split over the grid (fp32 slabs for the consumer)
 void launch_gemm_dec(int code, int depth, const bf16_t* X, int64_t ldx, const bf16_t* W, int64_t ldw,
                      const bf16_t* bias, bf16_t* Y, int64_t ldy, float* part, int M, int N, int K, int act, int glu,
-                     int split, hipStream_t st, const QkvEpi* qe, int* cnt);
+                     int split, hipStream_t st, const QkvEpi* qe, int* cnt, bool packed = false);
 bool gemm_dec_bn(int code, int* bn);
 // the decode GEMM's in-launch combine (hint bit 256 with a split) fits the workspace: [tile][split][64 * bn] fp32
 static bool dec_combine_fits(int N, int tsel, int s, int64_t ws_bytes) {
@@ -1379,6 +1379,32 @@ static bool dec_combine_fits(int N, int tsel, int s, int64_t ws_bytes) {
   return (int64_t)((N + bn - 1) / bn) * s * 64 * bn * 4 <= ws_bytes;
 }
 static constexpr int kDecHint = 1024;
+// packed weights (hint tile bit 2048, nt_hint bit 19): the weight pointer is the panel-packed copy of W,
+// [ceil(N/16)][ceil(K/64)][16][64] bf16 with zeros past N and K (csrc/pack.hip, ops.hip.pack_panels). gemm_dec and the
+// 64-row gemm_mid tiles have the variant, for bf16 weights at M <= 64; the output is bit-identical to the same hint
+// without the bit. launch_gemm / launch_gemm_qkv take the packed copy as `w_packed` next to the row-major `w`: an
+// explicit hint with the bit and no packed copy, fp8 weights, M > 64 or a kernel without the variant throw; a TUNED
+// plan with the bit (gemm_tuned_set) called without a packed copy runs its row-major sibling - the same kernel, the
+// same bits - so a caller that never made a packed twin is not broken by another caller's tuning.
+static constexpr int kPackedHint = 2048;
+// gemm_dec and the gemm_mid tiles stage and zero their K tail in 16-byte chunks, so a hint that names one of them
+// takes any K % 8 == 0; every other kernel needs K % 16 == 0
+static bool k_ok(int K, int nt_hint) {
+  const int t = nt_hint >> 8;
+  return K % 16 == 0 || (K % 8 == 0 && !(nt_hint & 0xff) && !(t & 128) && ((t & kDecHint) || (t & 15) >= 7));
+}
+static const void* packed_select(const void* w, const void* w_packed, bool tuned, bool w_fp8, int M, int* nt_hint) {
+  if (!((*nt_hint >> 8) & kPackedHint)) return w;
+  if (!w_packed && tuned) {
+    *nt_hint &= ~(kPackedHint << 8);
+    return w;
+  }
+  if (!w_packed) throw std::runtime_error("gemm: the packed-weight hint (bit 2048) needs the packed copy of the weight");
+  if (w_fp8) throw std::runtime_error("gemm: packed weights are bf16 only (no fp8 variant)");
+  if (M > 64) throw std::runtime_error("gemm: packed weights serve M <= 64 only");
+  if (*nt_hint & 0xff) throw std::runtime_error("gemm: the streaming kernels have no packed-weight variant");
+  return w_packed;
+}
 static int dec_split(int M, int N, int K, int split_hint, int64_t ws_bytes) {
   int s = std::max(1, std::min(split_hint, (K + 63) / 64));
   if ((int64_t)s * M * N * 4 > ws_bytes) s = 1;
@@ -1389,7 +1415,7 @@ void launch_gemm_mid(int tsel, int depth, bool wnt, const bf16_t* X, int64_t ldx
                      const bf16_t* bias, bf16_t* Y, int64_t ldy, float* part, int M, int N, int K, int act, int glu,
                      int split, hipStream_t st, int* cnt = nullptr,
                      const QkvEpi* qe = nullptr, const float* xs = nullptr, const float* wsc = nullptr,
-                     bool ilv = false, const unsigned char* asc = nullptr);
+                     bool ilv = false, const unsigned char* asc = nullptr, bool packed = false);
 
 // tile: 1 = 128x128, 2 = 64x128, 3 = 64x64; ring depth 2-4; split-K over grid.y; 8-13: the gemm_mid tiles
 // (buffer-descriptor staging, csrc/gemm_mid.hip, fp8 MFMA variant; K % 128 == 0; ilv: its software-pipelined
@@ -1616,12 +1642,15 @@ bool gemm_tuned_get(int M, int N, int K, bool glu, int kind, int* nt_hint, int* 
 
 int launch_gemm(const void* x, int64_t ldx, const void* w, int64_t ldw, bool w_fp8, const void* w_scale,
                 const void* bias, void* y, int64_t ldy, int M, int N, int K, int act, bool glu, void* workspace,
-                int64_t ws_bytes, int nt_hint, int split_hint, bool partial_out, hipStream_t st) {
+                int64_t ws_bytes, int nt_hint, int split_hint, bool partial_out, hipStream_t st,
+                const void* w_packed) {
   if (M == 0 || N == 0) return 0;
-  if (nt_hint == 0 && split_hint == 0) gemm_tuned_get(M, N, K, glu, w_fp8 ? 1 : 0, &nt_hint, &split_hint);
+  bool tuned = false;
+  if (nt_hint == 0 && split_hint == 0) tuned = gemm_tuned_get(M, N, K, glu, w_fp8 ? 1 : 0, &nt_hint, &split_hint);
+  w = packed_select(w, w_packed, tuned, w_fp8, M, &nt_hint);
   if (!y && (!partial_out || gemm_partial_slabs(M, N, K, w_fp8, glu, act, nt_hint, split_hint, ws_bytes) == 0))
     throw std::runtime_error("gemm: this configuration writes the output, but no output buffer was given");
-  if (K % 16) throw std::runtime_error("gemm: K must be a multiple of 16");
+  if (!k_ok(K, nt_hint)) throw std::runtime_error("gemm: K must be a multiple of 16 (of 8 on gemm_dec / gemm_mid hints)");
   if (glu && (N % 32)) throw std::runtime_error("gemm: glu needs N % 32 == 0");
   auto X = (const bf16_t*)x;
   auto B = (const bf16_t*)bias;
@@ -1637,7 +1666,7 @@ int launch_gemm(const void* x, int64_t ldx, const void* w, int64_t ldw, bool w_f
       for (int m0 = 0; m0 < M; m0 += 128) {
         const int mm = std::min(128, M - m0);
         launch_gemm((const bf16_t*)x + m0 * ldx, ldx, w, ldw, w_fp8, w_scale, bias, (bf16_t*)y + m0 * ldy, ldy, mm, N,
-                    K, act, glu, workspace, ws_bytes, nt_hint, split_hint, false, st);
+                    K, act, glu, workspace, ws_bytes, nt_hint, split_hint, false, st, nullptr);
       }
       return 0;
     }
@@ -1833,6 +1862,8 @@ int launch_tiled(const bf16_t* X, int64_t ldx, const void* W, int64_t ldw, const
   const int tsel_raw = tsel;
   int s = split_hint;
   const bool f8 = wscale != nullptr;  // fp8-e4m3 weights (W8A16): half the weight bytes of a decode step
+  const bool packed = (tsel & kPackedHint) != 0;  // W is the panel-packed copy (kPackedHint)
+  if (packed && (f8 || M > 64)) throw std::runtime_error("gemm: packed weights serve bf16 weights at M <= 64 only");
   if (tsel & kDecHint) {  // K split over the waves (gemm_dec.hip), M <= 64, bf16 weights
     if (f8) throw std::runtime_error("gemm_dec: bf16 weights only");
     s = dec_split(M, N, K, split_hint, ws_bytes);
@@ -1841,14 +1872,14 @@ int launch_tiled(const bf16_t* X, int64_t ldx, const void* W, int64_t ldw, const
       gemm_dec_bn(tsel & 15, &bn);
       static constexpr int kDecDepthC[4] = {2, 3, 4, 4};
       launch_gemm_dec(tsel & 15, kDecDepthC[(tsel >> 4) & 3], X, ldx, (const bf16_t*)W, ldw, B, Y, ldy,
-                      (float*)workspace, M, N, K, act, g, s, st, qe, sk_counters((N + bn - 1) / bn));
+                      (float*)workspace, M, N, K, act, g, s, st, qe, sk_counters((N + bn - 1) / bn), packed);
       return 0;
     }
     if (qe && s > 1) throw std::runtime_error("gemm_dec: the QKV epilogue needs an unsplit or in-launch-combined plan");
     static constexpr int kDecDepth[4] = {2, 3, 4, 4};
     float* part = s > 1 ? (float*)workspace : nullptr;
     launch_gemm_dec(tsel & 15, kDecDepth[(tsel >> 4) & 3], X, ldx, (const bf16_t*)W, ldw, B, Y, ldy, part, M, N, K,
-                    s > 1 ? 0 : act, s > 1 ? 0 : g, s, st, qe, nullptr);
+                    s > 1 ? 0 : act, s > 1 ? 0 : g, s, st, qe, nullptr, packed);
     if (s > 1 && partial_out && !g && act == 0) return s;
     if (s > 1) {
       const int nout = g ? N / 2 : N;
@@ -1863,6 +1894,8 @@ int launch_tiled(const bf16_t* X, int64_t ldx, const void* W, int64_t ldw, const
   static constexpr int kDepth[4] = {2, 3, 4, 6};
   int ns = kDepth[(tsel >> 4) & 3];  // LDS ring depth (hint bits 4-5); bit 6: default-policy weights
   tsel &= 15;
+  if (packed && (tsel < 7 || (tsel_raw & 128)))
+    throw std::runtime_error("gemm: this kernel has no packed-weight variant (gemm_dec and 64-row gemm_mid tiles only)");
   // the ping-pong kernel's zero-page K tail works on 8-element chunks and its LDS-DMA rows need 16-B aligned
   // strides: anything else runs on the 128x128 tile (tuned hints and C++ callers included, not just linear())
   if (tsel == 4 && (K % 8 || ldx % 8 || ldw % 8)) tsel = 1;
@@ -1899,7 +1932,7 @@ int launch_tiled(const bf16_t* X, int64_t ldx, const void* W, int64_t ldw, const
   dim3 grid(nt, s);
   if (tsel >= 7 && tsel <= 15) {  // gemm_mid tiles (7, 8-15)
     launch_gemm_mid(tsel, ns, wnt_ok(tsel_raw, M, tsel), X, ldx, (const bf16_t*)W, ldw, B, Y, ldy, part, M, N, K,
-                    act_k, glu_k, s, st, cnt, qe, nullptr, nullptr, (tsel_raw & 512) != 0);
+                    act_k, glu_k, s, st, cnt, qe, nullptr, nullptr, (tsel_raw & 512) != 0, nullptr, packed);
     if (cnt) return 0;
     if (s > 1 && partial_out && !g && act == 0) return s;
     if (s > 1) {
@@ -2011,14 +2044,17 @@ int gemm_partial_slabs(int M, int N, int K, bool w_fp8, bool glu, int act, int n
 // the caller then runs the plain GEMM and the rope_cache kernel; 0 when launched.
 int launch_gemm_qkv(const void* x, int64_t ldx, const void* w, int64_t ldw, const void* bias, void* y, int64_t ldy,
                     int M, int N, int K, void* workspace, int64_t ws_bytes, int nt_hint, int split_hint,
-                    const QkvEpi& qe, hipStream_t st) {
+                    const QkvEpi& qe, hipStream_t st, const void* w_packed) {
   if (M == 0) return 0;
   if (qe.D <= 0) return -1;
   if (!y) throw std::runtime_error("gemm_qkv: output buffer required");
-  if (K % 16) throw std::runtime_error("gemm_qkv: K must be a multiple of 16");
   if (qe.D % 8 || N != (qe.nh + 2 * qe.nkv) * qe.D || N % 8 || ldy % 8) return -1;
   if (qe.do_rope && (qe.rot % 8 || qe.rot > qe.D || (qe.style == 0 && qe.rot % 16))) return -1;
-  if (nt_hint == 0 && split_hint == 0) gemm_tuned_get(M, N, K, false, 3, &nt_hint, &split_hint);
+  bool tuned = false;
+  if (nt_hint == 0 && split_hint == 0) tuned = gemm_tuned_get(M, N, K, false, 3, &nt_hint, &split_hint);
+  if (!k_ok(K, nt_hint))
+    throw std::runtime_error("gemm_qkv: K must be a multiple of 16 (of 8 on gemm_dec / gemm_mid hints)");
+  w = packed_select(w, w_packed, tuned, false, M, &nt_hint);
   if (nt_hint & 0xff) return -1;  // streaming kernels have no LDS-staged epilogue
   if ((nt_hint >> 8) & kDecHint) {  // decode GEMM: unsplit, or split and combined in the launch (finished sums)
     int bn;
@@ -2049,10 +2085,12 @@ int launch_gemm_qkv(const void* x, int64_t ldx, const void* w, int64_t ldw, cons
 int launch_gemm_qkv_args(const void* x, int64_t ldx, const void* w, int64_t ldw, const void* bias, void* y, int64_t ldy,
                          int M, int N, int K, void* workspace, int64_t ws_bytes, int nt_hint, int split_hint,
                          const void* pos, const void* cos_t, const void* sin_t, void* kc, void* vc, const void* slot,
-                         int nh, int nkv, int D, int rot, int block_size, int style, bool do_rope, hipStream_t st) {
+                         int nh, int nkv, int D, int rot, int block_size, int style, bool do_rope, hipStream_t st,
+                         const void* w_packed) {
   const QkvEpi qe{(const int64_t*)pos, (const float*)cos_t, (const float*)sin_t, (bf16_t*)kc, (bf16_t*)vc,
                   (const int64_t*)slot, nh, nkv, D, rot, block_size, style, do_rope ? 1 : 0};
-  return launch_gemm_qkv(x, ldx, w, ldw, bias, y, ldy, M, N, K, workspace, ws_bytes, nt_hint, split_hint, qe, st);
+  return launch_gemm_qkv(x, ldx, w, ldw, bias, y, ldy, M, N, K, workspace, ws_bytes, nt_hint, split_hint, qe, st,
+                         w_packed);
 }
 
 void gemm_plan(int M, int N, int K, bool w_fp8, int* nt, int* splitk) {

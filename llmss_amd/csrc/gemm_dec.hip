@@ -21,6 +21,13 @@
 // Rows past M and columns past N read as zero through the buffer descriptors' range check; a partial last
 // k-step (K % 64 != 0) folds k into the voffset (the check covers voffset) and zeroes the A chunks past K in the
 // owning wave's slot, as gemm_mid does.
+//
+// PK (hint bit 2048, launch_gemm): B is the panel-packed copy of the weight, [ceil(N/16)][ceil(K/64)][16][64] bf16 with
+// zeros past N and K (pack_panels, csrc/pack.hip): one k-step of 16 columns is one contiguous 2-KiB block, which streams
+// from HBM at 6 TB/s where the 128-B pieces of rows 2 * ldb bytes apart reach ~5 (profiles/packed_decode). Only the
+// B addressing differs - per-lane offset (row / 16) * nk * 2048 + (row % 16) * 128 + swizzled chunk, k-step stride
+// 2048, range = the packed bytes from the tile's first panel; the LDS image and everything after it are the same, so
+// a packed plan's output is bit-identical to its row-major sibling's.
 #include "common.h"
 
 namespace {
@@ -94,7 +101,7 @@ __device__ __forceinline__ bool dec_combine(float* ct, float* ws, int* cnt, int 
 
 // MODE (bench/proto/dec_probe.hip only; the library instantiates 0): 1 = weight (B) loads only, 2 = activation (A)
 // loads only, 3 = no loads (MFMAs on whatever LDS holds), 4 = no epilogue stores - to take a launch's time apart.
-template <int MT, int BN, int NSW, int MODE = 0>
+template <int MT, int BN, int NSW, int MODE = 0, bool PK = false>
 __global__ __launch_bounds__(256) void gemm_dec_kernel(const bf16_t* __restrict__ A, int64_t lda,
                                                        const bf16_t* __restrict__ B, int64_t ldb,
                                                        const bf16_t* __restrict__ bias, bf16_t* __restrict__ Y,
@@ -122,11 +129,13 @@ __global__ __launch_bounds__(256) void gemm_dec_kernel(const bf16_t* __restrict_
   const bool ktail = (K & 63) != 0;
 
   const uint64_t abytes = (uint64_t)M * (uint64_t)lda * 2;
-  const uint64_t bbytes = (uint64_t)(N - n0) * (uint64_t)ldb * 2;
+  const uint64_t bbytes = PK ? (uint64_t)((N + 15) / 16 - n0 / 16) * (uint64_t)nk_all * 2048
+                             : (uint64_t)(N - n0) * (uint64_t)ldb * 2;
+  const int64_t bbase = PK ? (int64_t)(n0 / 16) * nk_all * 2048 : (int64_t)n0 * ldb * 2;  // bytes
   const auto ra = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(reinterpret_cast<const char*>(A)), (short)0,
                                                     (int)(abytes > 0xFFFFFFF0ull ? 0xFFFFFFF0u : (uint32_t)abytes),
                                                     0x00020000);
-  const auto rb = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(reinterpret_cast<const char*>(B) + (int64_t)n0 * ldb * 2),
+  const auto rb = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(reinterpret_cast<const char*>(B) + bbase),
                                                     (short)0,
                                                     (int)(bbytes > 0xFFFFFFF0ull ? 0xFFFFFFF0u : (uint32_t)bbytes),
                                                     0x00020000);
@@ -139,7 +148,8 @@ __global__ __launch_bounds__(256) void gemm_dec_kernel(const bf16_t* __restrict_
 #pragma unroll
   for (int i = 0; i < BL; ++i) {
     const int row = i * 8 + (lane >> 3);
-    vb[i] = (uint32_t)(row * ldb * 2 + (((lane & 7) ^ (row & 7)) << 4));
+    vb[i] = (PK ? (uint32_t)((row >> 4) * nk_all * 2048 + (row & 15) * 128) : (uint32_t)(row * ldb * 2)) +
+            (uint32_t)(((lane & 7) ^ (row & 7)) << 4);
   }
   char* ring = smem + w * (NSW * SLOT);
 
@@ -150,7 +160,7 @@ __global__ __launch_bounds__(256) void gemm_dec_kernel(const bf16_t* __restrict_
   do {                                                                                                           \
     const int t_ = t0 + w + NW * (J_);                                                                           \
     char* sl_ = ring + ((J_) % NSW) * SLOT;                                                                      \
-    const uint32_t so_ = (uint32_t)t_ * 128u;                                                                    \
+    const uint32_t so_ = (uint32_t)t_ * 128u, sob_ = (uint32_t)t_ * (PK ? 2048u : 128u);                         \
     if (MODE == 3) {                                                                                             \
     } else if (!ktail || t_ != nk_all - 1) {                                                                     \
       if (MODE != 1) _Pragma("unroll") for (int i_ = 0; i_ < AL; ++i_)                                           \
@@ -158,14 +168,14 @@ __global__ __launch_bounds__(256) void gemm_dec_kernel(const bf16_t* __restrict_
                                                  (uint32_t)so_, 0, 0);                                           \
       if (MODE != 2) _Pragma("unroll") for (int i_ = 0; i_ < BL; ++i_) /* weights: read once, non-temporal */    \
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, (LDS_AS void*)(sl_ + AR * 128 + i_ * 1024), 16,             \
-                                                 (uint32_t)vb[i_], (uint32_t)so_, 0, 2);                          \
+                                                 (uint32_t)vb[i_], (uint32_t)sob_, 0, 2);                         \
     } else { /* partial last k-step: k in the voffset, so the range check covers the last row's tail */         \
       _Pragma("unroll") for (int i_ = 0; i_ < AL; ++i_)                                                          \
         __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (LDS_AS void*)(sl_ + i_ * 1024), 16,                        \
                                                  (uint32_t)(va[i_] + so_), (uint32_t)0, 0, 0);                   \
       _Pragma("unroll") for (int i_ = 0; i_ < BL; ++i_)                                                          \
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, (LDS_AS void*)(sl_ + AR * 128 + i_ * 1024), 16,             \
-                                                 (uint32_t)(vb[i_] + so_), (uint32_t)0, 0, 2);                   \
+                                                 (uint32_t)(vb[i_] + sob_), (uint32_t)0, 0, 2);                  \
     }                                                                                                            \
   } while (0)
 
@@ -267,9 +277,12 @@ __global__ __launch_bounds__(256) void gemm_dec_kernel(const bf16_t* __restrict_
 template <int MT, int BN, int NS>
 static void dec_launch(dim3 grid, hipStream_t st, const bf16_t* X, int64_t ldx, const bf16_t* W, int64_t ldw,
                        const bf16_t* bias, bf16_t* Y, int64_t ldy, float* part, int M, int N, int K, int act, int glu,
-                       const QkvEpi& qv, int* cnt) {
+                       const QkvEpi& qv, int* cnt, bool packed) {
   if constexpr (NS > 2 && !DecCfg<MT, BN, NS>::FITS) {
-    dec_launch<MT, BN, NS - 1>(grid, st, X, ldx, W, ldw, bias, Y, ldy, part, M, N, K, act, glu, qv, cnt);
+    dec_launch<MT, BN, NS - 1>(grid, st, X, ldx, W, ldw, bias, Y, ldy, part, M, N, K, act, glu, qv, cnt, packed);
+  } else if (packed) {
+    gemm_dec_kernel<MT, BN, NS, 0, true><<<grid, 256, 0, st>>>(X, ldx, W, ldw, bias, Y, ldy, part, M, N, K, act, glu,
+                                                               qv, cnt);
   } else {
     gemm_dec_kernel<MT, BN, NS><<<grid, 256, 0, st>>>(X, ldx, W, ldw, bias, Y, ldy, part, M, N, K, act, glu, qv, cnt);
   }
@@ -293,14 +306,16 @@ static int dec_depth(int mt, int bn, int want) {
 
 // cnt != nullptr: split-K combined in the launch (dec_combine; `part` = the workspace holding [tile][split][64 * bn]
 // fp32 slabs, sized by the caller), finished output in Y with act / glu / the QKV epilogue
+// packed: W is the panel-packed copy (PK above; ldw is unused)
 void launch_gemm_dec(int code, int depth, const bf16_t* X, int64_t ldx, const bf16_t* W, int64_t ldw,
                      const bf16_t* bias, bf16_t* Y, int64_t ldy, float* part, int M, int N, int K, int act, int glu,
-                     int split, hipStream_t st, const QkvEpi* qe, int* cnt) {
+                     int split, hipStream_t st, const QkvEpi* qe, int* cnt, bool packed = false) {
   int bn;
   if (!gemm_dec_bn(code, &bn)) throw std::runtime_error("gemm_dec: bad tile code");
   if (M < 1 || M > 64) throw std::runtime_error("gemm_dec: M must be 1..64");
   if (glu && (bn % 32)) throw std::runtime_error("gemm_dec: SwiGLU needs 32-column tile pairs");
-  if ((uint64_t)64 * ldx * 2 >= (1ull << 31) || (uint64_t)bn * ldw * 2 >= (1ull << 31))
+  if ((uint64_t)64 * ldx * 2 >= (1ull << 31) || (!packed && (uint64_t)bn * ldw * 2 >= (1ull << 31)) ||
+      (packed && (uint64_t)(bn / 16 + 1) * ((K + 63) / 64) * 2048 >= (1ull << 31)))
     throw std::runtime_error("gemm_dec: row stride too large for 32-bit buffer offsets");
   const int mt = M <= 16 ? 1 : (M <= 32 ? 2 : 4);
   const int ns = dec_depth(mt, bn, depth);
@@ -308,9 +323,9 @@ void launch_gemm_dec(int code, int depth, const bf16_t* X, int64_t ldx, const bf
   dim3 grid((N + bn - 1) / bn, split);
 #define DECN(MT_, BN_)                                                                                           \
   do {                                                                                                           \
-    if (ns >= 4) dec_launch<MT_, BN_, 4>(grid, st, X, ldx, W, ldw, bias, Y, ldy, part, M, N, K, act, glu, qv, cnt);   \
-    else if (ns == 3) dec_launch<MT_, BN_, 3>(grid, st, X, ldx, W, ldw, bias, Y, ldy, part, M, N, K, act, glu, qv, cnt); \
-    else dec_launch<MT_, BN_, 2>(grid, st, X, ldx, W, ldw, bias, Y, ldy, part, M, N, K, act, glu, qv, cnt);          \
+    if (ns >= 4) dec_launch<MT_, BN_, 4>(grid, st, X, ldx, W, ldw, bias, Y, ldy, part, M, N, K, act, glu, qv, cnt, packed);   \
+    else if (ns == 3) dec_launch<MT_, BN_, 3>(grid, st, X, ldx, W, ldw, bias, Y, ldy, part, M, N, K, act, glu, qv, cnt, packed); \
+    else dec_launch<MT_, BN_, 2>(grid, st, X, ldx, W, ldw, bias, Y, ldy, part, M, N, K, act, glu, qv, cnt, packed);          \
   } while (0)
 #define DECB(MT_)                                                                                                \
   do {                                                                                                           \

@@ -39,8 +39,14 @@
 // row and 32-element block (OCP MX; asc [M][K / 32] bytes, written by a SwiGLU epilogue, img_store_rows) instead of
 // one fp32 scale per row. Each ring stage also stages the tile's 4 scale bytes per row of that k-step (one 4-byte
 // LDS-DMA piece per wave: its BM / NW rows); lane group g passes the byte of block g to the MX-fp8 MFMA.
+// PK (bf16, 64-row tiles at M <= 64; hint bit 2048 of launch_gemm): B is the panel-packed copy of the weight,
+// [ceil(N/16)][ceil(K/64)][16][64] with zeros past N and K (csrc/pack.hip). Only the B addressing changes - per-lane
+// offset (row / 16) * nk * 2048 + (row % 16) * 128 + swizzled chunk, k-step stride 2048, range = the packed bytes from
+// the tile's first panel - so every k-step of 16 columns is one contiguous 2-KiB read (6 TB/s from HBM against ~5 for
+// 128-B pieces of rows 2 * ldb apart, profiles/packed_decode); the LDS image and all that follows are unchanged, and
+// the output is bit-identical to the row-major plan's.
 template <int BM, int BN, int WM, int WN, int NS, bool WNT, bool F8 = false, int MODE = 0, bool ILV = false,
-          bool MXA = false>
+          bool MXA = false, bool PK = false>
 __global__ __launch_bounds__(64 * WM * WN) void gemm_mid_kernel(const bf16_t* __restrict__ A, int64_t lda,
                                                               const bf16_t* __restrict__ B, int64_t ldb,
                                                               const bf16_t* __restrict__ bias, bf16_t* __restrict__ Y,
@@ -49,6 +55,7 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_mid_kernel(const bf16_t* __
                                                               const float* __restrict__ xs,
                                                               const float* __restrict__ wsc,
                                                               const unsigned char* __restrict__ asc) {
+  static_assert(!PK || (!F8 && !ILV && !MXA && MODE == 0), "packed B: the plain bf16 ring only");
   constexpr int ES = F8 ? 1 : 2;  // operand bytes per element
   constexpr int NW = WM * WN;
   constexpr int MT = BM / WM / 16, NT = BN / WN / 16;  // 16x16 accumulator tiles per wave
@@ -76,8 +83,9 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_mid_kernel(const bf16_t* __
 
   // descriptors start at this tile's first row; everything past the matrix end reads as zero
   const uint64_t abytes = (uint64_t)(M - m0) * (uint64_t)lda * ES;
-  const uint64_t bbytes = (uint64_t)(N - n0) * (uint64_t)ldb * ES;
-  const int64_t boff = (int64_t)n0 * ldb * ES;  // bytes
+  const uint64_t bbytes = PK ? (uint64_t)((N + 15) / 16 - n0 / 16) * (uint64_t)nk_all * 2048
+                             : (uint64_t)(N - n0) * (uint64_t)ldb * ES;
+  const int64_t boff = PK ? (int64_t)(n0 / 16) * nk_all * 2048 : (int64_t)n0 * ldb * ES;  // bytes
   const auto ra = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<char*>(reinterpret_cast<const char*>(A) + (int64_t)m0 * lda * ES), (short)0,
       (int)(abytes > 0xFFFFFFF0ull ? 0xFFFFFFF0u : (uint32_t)abytes), 0x00020000);
@@ -99,7 +107,8 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_mid_kernel(const bf16_t* __
 #pragma unroll
   for (int i = 0; i < BL; ++i) {
     const int row = (i * NW + w) * 8 + (lane >> 3);
-    vb[i] = (uint32_t)(row * ldb * ES + (((lane & 7) ^ (row & 7)) << 4));
+    vb[i] = (PK ? (uint32_t)((row >> 4) * nk_all * 2048 + (row & 15) * 128) : (uint32_t)(row * ldb * ES)) +
+            (uint32_t)(((lane & 7) ^ (row & 7)) << 4);
   }
   // one ring stage (k-step T_) into LDS slot SA_: AL + BL wave-instructions of 1 KiB (8 rows x 128 B);
   // the k position is the scalar soffset, the per-lane voffsets never change
@@ -107,7 +116,7 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_mid_kernel(const bf16_t* __
   do {                                                                                                           \
     char* sA_ = (SA_);                                                                                           \
     if (MODE == 2) break;                                                                                        \
-    const int soff_ = (T_) * 128, sofb_ = soff_;                                                                  \
+    const int soff_ = (T_) * 128, sofb_ = PK ? (T_) * 2048 : soff_;                                               \
     if (!ktail || (T_) != nk_all - 1) {                                                                          \
       _Pragma("unroll") for (int i_ = 0; i_ < AL; ++i_)                                                           \
         __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (LDS_AS void*)(sA_ + (i_ * NW + w) * 1024), 16, (uint32_t)va[i_], (uint32_t)soff_, 0, 0); \
@@ -500,10 +509,20 @@ static int mid_depth(int bm, int bn, int want, int extra = 0) {
   return ns;
 }
 
+// the packed-B instantiations: 64-row tiles only (the host refuses the others before it gets here)
+template <int BM, int BN, int WM, int WN, int NS>
+static void mid_launch_packed(dim3 grid, hipStream_t st, const bf16_t* X, int64_t ldx, const bf16_t* W,
+                              const bf16_t* bias, bf16_t* Y, int64_t ldy, float* part, int M, int N, int K, int act,
+                              int glu, int* cnt, const QkvEpi& qv) {
+  if constexpr (BM == 64)
+    gemm_mid_kernel<BM, BN, WM, WN, NS, true, false, 0, false, false, true><<<grid, 64 * WM * WN, 0, st>>>(
+        X, ldx, W, 0, bias, Y, ldy, part, M, N, K, act, glu, cnt, qv, nullptr, nullptr, nullptr);
+}
+
 void launch_gemm_mid(int tsel, int depth, bool wnt, const bf16_t* X, int64_t ldx, const bf16_t* W, int64_t ldw,
                      const bf16_t* bias, bf16_t* Y, int64_t ldy, float* part, int M, int N, int K, int act, int glu,
                      int split, hipStream_t st, int* cnt, const QkvEpi* qe, const float* xs,
-                     const float* wsc, bool ilv, const unsigned char* asc) {
+                     const float* wsc, bool ilv, const unsigned char* asc, bool packed = false) {
   const bool f8 = xs != nullptr || asc != nullptr;
   if (f8 && (!wsc || K % 128)) throw std::runtime_error("gemm_mid fp8: per-row weight scales, K % 128 == 0");
   if (xs && asc) throw std::runtime_error("gemm_mid fp8: per-row activation scales or MX scales, not both");
@@ -512,8 +531,17 @@ void launch_gemm_mid(int tsel, int depth, bool wnt, const bf16_t* X, int64_t ldx
   if (!mid_layout(tsel, &bm, &bn, &wm, &wn)) throw std::runtime_error("gemm_mid: bad tile code");
   if (glu && (bn / wn / 16) % 2)
     throw std::runtime_error("gemm_mid: SwiGLU needs an even number of 16-column tiles per wave");
-  if ((uint64_t)bm * ldx * 2 >= (1ull << 31) || (uint64_t)bn * ldw * 2 >= (1ull << 31))
+  if ((uint64_t)bm * ldx * 2 >= (1ull << 31) || (!packed && (uint64_t)bn * ldw * 2 >= (1ull << 31)))
     throw std::runtime_error("gemm_mid: row stride too large for 32-bit buffer offsets");
+  if (packed) {  // W is the panel-packed copy (PK): bf16, the 64-row decode tiles, non-temporal weight loads
+    if (f8) throw std::runtime_error("gemm_mid: packed weights are bf16 only (no fp8 variant)");
+    if (bm != 64) throw std::runtime_error("gemm_mid: this tile has no packed-weight variant (64-row tiles only)");
+    if (M > 64) throw std::runtime_error("gemm_mid: packed weights serve M <= 64 only");
+    if (ilv) throw std::runtime_error("gemm_mid: the interleaved ring has no packed-weight variant");
+    if (!wnt) throw std::runtime_error("gemm_mid: packed weights are streamed non-temporally (hint bit 64 does not apply)");
+    if ((uint64_t)(bn / 16 + 1) * ((K + 63) / 64) * 2048 >= (1ull << 31))
+      throw std::runtime_error("gemm_mid: packed panel too large for 32-bit buffer offsets");
+  }
   const int ns = mid_depth(bm, bn, depth, asc ? wm * wn * 256 : 0);
   // the interleaved rings' preconditions; the fp8 one holds two fragment sets, which 8-wave tiles (256 VGPRs per
   // lane at two waves per SIMD) spill to scratch: 5-8x slower (profiles/r6_f8)
@@ -552,7 +580,9 @@ void launch_gemm_mid(int tsel, int depth, bool wnt, const bf16_t* X, int64_t ldx
                                         nullptr, nullptr)
 #define MID(BM_, BN_, WM_, WN_, NS_)                                                                             \
   do {                                                                                                         \
-    if (f8 && ilv && NS_ >= 3) {                                                                               \
+    if (packed) {                                                                                              \
+      mid_launch_packed<BM_, BN_, WM_, WN_, NS_>(grid, st, X, ldx, W, bias, Y, ldy, part, M, N, K, act, glu, cnt, qv); \
+    } else if (f8 && ilv && NS_ >= 3) {                                                                               \
       if (wnt) MID1F8I(BM_, BN_, WM_, WN_, NS_, true); else MID1F8I(BM_, BN_, WM_, WN_, NS_, false);          \
     } else if (f8) {                                                                                           \
       if (wnt) MID1F8(BM_, BN_, WM_, WN_, NS_, true); else MID1F8(BM_, BN_, WM_, WN_, NS_, false);            \

@@ -252,9 +252,60 @@ class LLMEngine:
             self.tuned = tune_model(model, self.decode_batch_sizes())
         if self.is_gpu and autotune:
             self._tune_gqa_attention()
+        self.stats["packed_weight_bytes"] = self._pack_decode_weights() if self.is_gpu else 0
         if self.use_graphs and os.environ.get("LLMSS_GRAPHS", "1") == "0":
             self.use_graphs = False
         self._capture_agreed()
+
+    def _pack_decode_weights(self) -> int:
+        """Panel-packed twins (ops.hip.pack_panels) of the projections whose plan at some decode row count reads
+        packed weights (hint bit 2048 in the native plan table: the autotuner's choice, or gemm_tuned_set). Made after
+        tuning and before graph capture, kept on the model's Linear objects for the model's lifetime - the captured
+        graphs hold their addresses. Prefill and every M > 64 call keep reading the row-major weight. The KV cache is
+        already sized, so ``num_blocks`` does not change; a projection whose twin would not leave 2 GiB free is skipped
+        (its packed plans then run their row-major siblings: the same kernels, the same bits). Returns the bytes added."""
+        from ..ops.autotune import PACKED
+
+        lib = _hip_ops.lib()
+        ms = [m for m in self.decode_batch_sizes() if m <= 64]
+        layers = self.model.w.layers
+        groups = [(name, [getattr(L, name) for L in layers]) for name in ("qkv", "o", "up", "down")]
+        groups.append(("head", [self.model.w.head]))
+        total = 0
+        for name, lins in groups:
+            lin = lins[0]
+            if lin.w_scale is not None or lin.w.dim() != 2 or lin.w.dtype != torch.bfloat16 or not lin.w.is_cuda:
+                continue
+            plans = {}
+            for m in ms:
+                for kind in ((0, 3) if name == "qkv" else (0,)):
+                    t = lib.gemm_tuned_get(m, lin.N, lin.K, bool(lin.glu), kind)
+                    if t is not None and t[0] & PACKED:
+                        plans[(m, kind)] = t
+            top = max(ms) if ms else 0
+            won = self.tuned.get(("qkv_epi" if (top, 3) in plans else name, top)) or self.tuned.get((name, top))
+            won_s = f"; tuner at M={top}: hint {won[0]:#x} split {won[1]} {won[2]:.1f} us (default {won[3]:.1f})" \
+                if won else ""
+            if not plans:
+                log.info("packed weights: %s [%d, %d] stays row-major in every decode bucket%s", name, lin.N, lin.K,
+                         won_s)
+                continue
+            need = sum(-(-l.N // 16) * -(-l.K // 64) * 2048 for l in lins if l.w_packed is None)
+            free, _ = torch.cuda.mem_get_info(self.device)
+            if need + (2 << 30) > free:
+                log.warning("packed weights: %s needs %.2f GB, %.2f GB free: kept row-major", name, need / 1e9,
+                            free / 1e9)
+                continue
+            for l in lins:
+                if l.w_packed is None:
+                    l.w_packed = _hip_ops.pack_panels(l.w)
+            total += need
+            log.info("packed weights: %s [%d, %d] x %d packed, +%.3f GB; plans %s%s", name, lin.N, lin.K, len(lins),
+                     need / 1e9, ", ".join(f"M={m}{'/qkv-epilogue' if k == 3 else ''}: hint {t[0]:#x} split {t[1]}"
+                                          for (m, k), t in sorted(plans.items())), won_s)
+        if total:
+            torch.cuda.synchronize(self.device)
+        return total
 
     def _capture_agreed(self):
         """Capture the decode graphs, agreeing on the outcome across TP ranks: if capture fails on ANY rank

@@ -222,7 +222,8 @@ class DecoderLM:
         if y.is_cuda and self.qkv_epi and not self.kv_fp8 and L.qkv.w.dim() == 2 and L.qkv.w_scale is None \
                 and _hip_ops().lib().gemm_tuned_get(y.shape[0], L.qkv.N, L.qkv.K, False, 3) is not None:
             out = _hip_ops().linear_qkv(y, L.qkv.w, L.qkv.b, inp.positions, self.w.cos, self.w.sin, kc, vc, inp.slots,
-                                        p.nh_l, p.nkv_l, cfg.head_dim, cfg.rotary_dim, cfg.rope_style, do_rope)
+                                        p.nh_l, p.nkv_l, cfg.head_dim, cfg.rotary_dim, cfg.rope_style, do_rope,
+                                        w_packed=L.qkv.w_packed)
             if out is not None:
                 return out
         qkv = L.qkv(y, partial_ok=True)

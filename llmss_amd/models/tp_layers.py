@@ -55,11 +55,12 @@ def as_group_view(group) -> ProcessGroupView:
     return group if isinstance(group, ProcessGroupView) else ProcessGroupView(group)
 
 
-def _linear2d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor]) -> torch.Tensor:
+def _linear2d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor],
+              weight_packed: Optional[torch.Tensor] = None) -> torch.Tensor:
     shp = x.shape
     x2 = x.reshape(-1, shp[-1])
     if x2.is_cuda and x2.dtype == torch.bfloat16 and weight.dtype == torch.bfloat16 and shp[-1] % 16 == 0:
-        y = ops.linear(x2.contiguous(), weight, bias)
+        y = ops.linear(x2.contiguous(), weight, bias, w_packed=weight_packed)
     else:  # CPU tensors / dtypes the MFMA kernels do not take
         y = torch.nn.functional.linear(x2, weight, bias)
     return y.reshape(*shp[:-1], weight.shape[0])
@@ -70,6 +71,16 @@ class FastLinear(nn.Module):
         super().__init__()
         self.weight = nn.Parameter(weight.contiguous(), requires_grad=False)
         self.bias = nn.Parameter(bias.contiguous(), requires_grad=False) if bias is not None else None
+        # optional panel-packed twin of the weight (pack()): decode plans with the packed hint (M <= 64) stream it,
+        # everything else reads self.weight; ignored on the CPU
+        self.weight_packed: Optional[torch.Tensor] = None
+
+    def pack(self) -> None:
+        """Make the packed twin (GPU bf16 weights only; a no-op elsewhere)."""
+        if self.weight.is_cuda and self.weight.dtype == torch.bfloat16 and self.weight_packed is None:
+            from ..ops import hip
+
+            self.weight_packed = hip.pack_panels(self.weight.data)
 
     @classmethod
     def load(cls, config, prefix: str, weights, bias: bool):
@@ -78,7 +89,7 @@ class FastLinear(nn.Module):
         return cls(w, b)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        return _linear2d(x, self.weight, self.bias)
+        return _linear2d(x, self.weight, self.bias, self.weight_packed)
 
 
 def get_linear(weight, bias):

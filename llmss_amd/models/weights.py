@@ -78,9 +78,13 @@ class Linear:
     b: Optional[torch.Tensor] = None
     w_scale: Optional[torch.Tensor] = None
     glu: bool = False
+    # panel-packed twin of a bf16 w (ops.hip.pack_panels), made by the engine after tuning for projections whose
+    # decode plan streams it; prefill and every M > 64 call read w
+    w_packed: Optional[torch.Tensor] = None
 
     def __call__(self, x, act="none", partial_ok=False):
-        return ops.linear(x, self.w, self.b, act, self.glu, self.w_scale, partial_ok=partial_ok)
+        return ops.linear(x, self.w, self.b, act, self.glu, self.w_scale, partial_ok=partial_ok,
+                          w_packed=self.w_packed)
 
     @property
     def N(self) -> int:

@@ -89,10 +89,12 @@ def attn_extend(q, k_cache, v_cache, block_tables, cu_q, ctx_lens, max_qlen, nh,
                                  kv_starts=kv_starts), out)
 
 
-def linear(x, w, bias=None, act="none", glu=False, w_scale: Optional[torch.Tensor] = None, partial_ok=False):
-    """partial_ok: on GPU the result may be a split-K PartialSum that only add_norm consumes."""
+def linear(x, w, bias=None, act="none", glu=False, w_scale: Optional[torch.Tensor] = None, partial_ok=False,
+           w_packed=None):
+    """partial_ok: on GPU the result may be a split-K PartialSum that only add_norm consumes. w_packed: the panel-packed
+    twin of ``w`` (ops.hip.pack_panels) for decode plans that stream it; the CPU path ignores it."""
     if x.is_cuda:
-        return _hip().linear(x, w, bias, act, glu, w_scale, partial_ok=partial_ok)
+        return _hip().linear(x, w, bias, act, glu, w_scale, partial_ok=partial_ok, w_packed=w_packed)
     return ref.linear(x, w, bias, act, glu, w_scale)
 
 

@@ -622,10 +622,40 @@ def dequant_fp8_rows(q, scale, out=None):
     return w
 
 
+PACKED_HINT = 2048 << 8  # nt_hint bit 19: the plan streams the panel-packed copy of the weight (csrc/gemm.hip)
+
+
+def pack_panels(w, out=None):
+    """Panel-packed copy ``[ceil(N/16)][ceil(K/64)][16][64]`` of a row-major bf16 ``[N, K]`` weight of any row stride,
+    zeros past N and K (csrc/pack.hip; bit-equal to ``reference.pack_panels``): what a plan with :data:`PACKED_HINT`
+    reads. Made once per weight; the decode GEMMs at M <= 64 stream it at the full HBM rate."""
+    _check(w.is_cuda and w.device.index == torch.cuda.current_device(), "w must be on the current GPU")
+    _check(w.dtype == torch.bfloat16 and w.dim() == 2 and w.stride(1) == 1 and w.stride(0) >= w.shape[1],
+           "w must be bf16 [N, K] with contiguous rows")
+    N, K = w.shape
+    shape = (-(-N // 16), -(-K // 64), 16, 64)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.bfloat16, device=w.device)
+    _check(tuple(out.shape) == shape and out.dtype == torch.bfloat16 and out.is_contiguous() and out.device == w.device,
+           f"out must be a contiguous bf16 {shape}")
+    lib().pack_panels(w.data_ptr(), w.stride(0), out.data_ptr(), N, K, _stream())
+    return out
+
+
+def _packed_ptr(w_packed, N, K, device) -> int:
+    if w_packed is None:
+        return 0
+    _check(w_packed.dtype == torch.bfloat16 and w_packed.is_contiguous() and w_packed.device == device
+           and tuple(w_packed.shape) == (-(-N // 16), -(-K // 64), 16, 64),
+           "w_packed must be pack_panels(w): contiguous bf16 [ceil(N/16), ceil(K/64), 16, 64] on x's device")
+    return w_packed.data_ptr()
+
+
 def linear(x, w, bias=None, act="none", glu=False, w_scale=None, out=None, nt_hint=0, split_hint=0,
-           partial_ok=False, mx_out=False):
+           partial_ok=False, mx_out=False, w_packed=None):
     """``x`` bf16 [M, K], or an :class:`MxAct` for an fp8 weight with a W8A8 gemm_mid plan; ``mx_out``: return an
-    fp8 SwiGLU output as :class:`MxAct` (its plan must allow it: :func:`mx_mlp_ok`)."""
+    fp8 SwiGLU output as :class:`MxAct` (its plan must allow it: :func:`mx_mlp_ok`). ``w_packed``: the
+    :func:`pack_panels` twin of ``w``; a plan (hint or tuned) with :data:`PACKED_HINT` reads it instead of ``w``."""
     M, K = x.shape
     if isinstance(x, MxAct) or mx_out:
         _check(w_scale is not None, "MX-fp8 activations need fp8 weights")
@@ -653,7 +683,8 @@ def linear(x, w, bias=None, act="none", glu=False, w_scale=None, out=None, nt_hi
         _check(w.is_contiguous(), "w contiguous")
     N = w.shape[0]
     _check(w.shape[1] == K, f"weight K={w.shape[1]} != x K={K}")
-    _check(K % 16 == 0, "K must be a multiple of 16")
+    # gemm_dec / gemm_mid hints take K % 8 == 0 (16-byte K-tail chunks); the library checks the plan it really runs
+    _check(K % 16 == 0 or (K % 8 == 0 and nt_hint), "K must be a multiple of 16")
     if glu:
         _check(N % 32 == 0, "glu needs N % 32 == 0")
     if bias is not None:
@@ -669,7 +700,8 @@ def linear(x, w, bias=None, act="none", glu=False, w_scale=None, out=None, nt_hi
         _bf16_rows(y, "out", nout)
     S = lib().gemm(x.data_ptr(), x.stride(0), w.data_ptr(), K, fp8, _ptr(w_scale), _ptr(bias), _ptr(y),
                    y.stride(0) if y is not None else nout, M, N, K, _ACT[act], bool(glu), ws.data_ptr(),
-                   ws.numel() * 4, int(nt_hint), int(split_hint), bool(y is None), _stream())
+                   ws.numel() * 4, int(nt_hint), int(split_hint), bool(y is None), _stream(),
+                   _packed_ptr(w_packed, N, K, x.device) if M <= 64 or nt_hint else 0)
     if y is None:
         if S <= 1:
             raise RuntimeError("internal: partial GEMM did not produce partial slabs")
@@ -678,7 +710,7 @@ def linear(x, w, bias=None, act="none", glu=False, w_scale=None, out=None, nt_hi
 
 
 def linear_qkv(x, w, bias, positions, cos, sin, k_cache, v_cache, slots, nh, nkv, D, rot, style, do_rope=True,
-               nt_hint=0, split_hint=0):
+               nt_hint=0, split_hint=0, w_packed=None):
     """QKV projection whose GEMM epilogue applies RoPE and writes k / v into the paged cache (one launch
     instead of GEMM + rope_cache; same values). Returns the bf16 [T, N] qkv tensor, or None when this
     weight / cache / plan cannot take the fused epilogue (packed or fp8 weights, fp8 KV rows, streaming or
@@ -710,7 +742,7 @@ def linear_qkv(x, w, bias, positions, cos, sin, k_cache, v_cache, slots, nh, nkv
                         ws.data_ptr(), ws.numel() * 4, int(nt_hint), int(split_hint), positions.data_ptr(),
                         _ptr(cos) if do_rope else 0, _ptr(sin) if do_rope else 0, _ptr(k_cache), _ptr(v_cache),
                         _ptr(slots) if k_cache is not None else 0, nh, nkv, D, rot, bs, 1 if style == "gptj" else 0,
-                        do_rope, _stream())
+                        do_rope, _stream(), _packed_ptr(w_packed, N, K, x.device) if M <= 64 or nt_hint else 0)
     return y if rc == 0 else None
 
 

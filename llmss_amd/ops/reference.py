@@ -340,6 +340,23 @@ def linear(x: torch.Tensor, w: torch.Tensor, bias=None, act: str = "none", glu: 
     return y.to(x.dtype)
 
 
+def pack_panels(w: torch.Tensor) -> torch.Tensor:
+    """Panel-packed copy of a row-major ``[N, K]`` weight for the decode GEMMs: ``[ceil(N/16)][ceil(K/64)][16][64]``,
+    element ``(n, k)`` at ``[n // 16, k // 64, n % 16, k % 64]``, zeros past N and K. One k-step of 16 columns is one
+    contiguous 2-KiB block, which the decode kernels stream at the full HBM rate (profiles/packed_decode)."""
+    N, K = w.shape
+    NP, KP = -(-N // 16), -(-K // 64)
+    p = torch.zeros(NP * 16, KP * 64, dtype=w.dtype, device=w.device)
+    p[:N, :K] = w
+    return p.view(NP, 16, KP, 64).permute(0, 2, 1, 3).contiguous()
+
+
+def unpack_panels(p: torch.Tensor, N: int, K: int) -> torch.Tensor:
+    """Inverse of :func:`pack_panels`: the row-major ``[N, K]`` weight."""
+    NP, KP = p.shape[0], p.shape[1]
+    return p.permute(0, 2, 1, 3).reshape(NP * 16, KP * 64)[:N, :K].contiguous()
+
+
 def quant_fp8_rows(w: torch.Tensor):
     wf = w.float()
     amax = wf.abs().amax(dim=1).clamp_min(0)
