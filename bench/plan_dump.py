@@ -12,6 +12,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from llmss_amd.ops import autotune as A  # noqa: E402
 from llmss_amd.ops import hip as H  # noqa: E402
+from llmss_amd.ops.plans import describe  # noqa: E402
 
 
 def main():
@@ -47,7 +48,7 @@ def main():
     wb = a.N * a.K * 2
     print(f"M={a.M} N={a.N} K={a.K} glu={a.glu} partial={a.partial}: {len(rows)} plans")
     for t, nt, s, slabs in rows[:a.top]:
-        print(f"  0x{nt:x}/s{s}  {t:6.1f} us  {wb / t / 1e6:5.2f} TB/s  slabs {slabs}")
+        print(f"  0x{nt:x}/s{s}  {t:6.1f} us  {wb / t / 1e6:5.2f} TB/s  slabs {slabs}  {describe(nt, s)}")
 
 
 if __name__ == "__main__":

@@ -8,6 +8,8 @@
 #include <pybind11/pybind11.h>
 #include <stdint.h>
 
+#include "gemm_plan.h"
+
 namespace py = pybind11;
 
 void launch_add_norm(const void* x, int64_t x_stride, const void* res_in, void* res_out, const void* w, const void* b,
@@ -54,23 +56,16 @@ int launch_gemm(const void* x, int64_t ldx, const void* w, int64_t ldw, bool w_f
                 int64_t ws_bytes, int nt_hint, int split_hint, bool partial_out, hipStream_t st,
                 const void* w_packed);
 void launch_pack_panels(const void* w, int64_t ld, void* p, int64_t N, int64_t K, hipStream_t st);
-void gemm_plan(int M, int N, int K, bool w_fp8, int* nt, int* splitk);
-void gemm_tuned_set(int M, int N, int K, bool glu, int kind, int nt_hint, int split);
-void gemm_tuned_clear();
 void gemm_reserve_streamk(int n);
 void gemm_set_slot(int s);
 int launch_gemm_f8f8(const void* xq, int64_t ldx, const void* xs, const void* wq, int64_t ldw, const void* wsc,
                      const void* bias, void* y, int64_t ldy, int M, int N, int K, int act, bool glu, int tile,
                      int depth, int split, void* workspace, int64_t ws_bytes, hipStream_t st, bool partial_out,
                      bool ilv, void* mxq, void* mxs, const void* asc);
-int gemm_f8f8_partial_slabs(int M, int N, int K, bool glu, int act, int tile, int split, int64_t ws_bytes);
-int gemm_partial_slabs(int M, int N, int K, bool w_fp8, bool glu, int act, int nt_hint, int split_hint,
-                       int64_t ws_bytes);
 void attn_decode_set_unroll(int u);
 void launch_comm_model(void* buf, int channels, int64_t nbytes, double us, hipStream_t st);
 int64_t comm_model_slice(int channels, int64_t nbytes);
 
-bool gemm_tuned_get(int M, int N, int K, bool glu, int kind, int* nt_hint, int* split);
 void launch_add_norm_partial(const void* part, int S, int64_t slab, const void* xbias, const void* res_in,
                              void* res_out, const void* w, const void* b, void* y, int64_t y_stride, int T, int H,
                              float eps, bool rms, hipStream_t st, void* q8, void* s8);
@@ -188,6 +183,29 @@ PYBIND11_MODULE(_C, m) {
     gemm_plan(M, N, K, fp8, &nt, &s);
     return py::make_tuple(nt, s);
   });
+  // the launch a call with these arguments resolves to (gemm_plan.h GemmExec), as a dict; raises what the call would
+  m.def("gemm_resolve", [](int M, int N, int K, bool fp8, bool glu, int act, int64_t ws_bytes, int nt_hint,
+                           int split_hint, bool tuned, bool has_out, bool partial_out, bool has_packed, int qkv_D,
+                           bool neox, bool rope, bool aligned) {
+    static const char* const kFamily[] = {"none", "stream", "stream_panels", "tiled", "wide8", "ping_pong", "stream_k",
+                                          "mid", "dec", "f8_big", "f8_tiled"};
+    static const char* const kFinish[] = {"kernel", "combine", "slabs", "reduce"};
+    const QkvFacts qf{qkv_D, neox, rope};
+    const GemmExec e = gemm_resolve({M, N, K, fp8, glu, act, ws_bytes, has_out, partial_out, has_packed,
+                                     qkv_D > 0 ? &qf : nullptr, aligned, nt_hint, split_hint, tuned});
+    py::dict d;
+    d["family"] = kFamily[(int)e.family];
+    d["finish"] = kFinish[(int)e.finish];
+    d["tile"] = e.tile; d["bm"] = e.bm; d["bn"] = e.bn; d["threads"] = e.threads; d["depth"] = e.depth;
+    d["split"] = e.split; d["wnt"] = e.wnt; d["ilv"] = e.ilv; d["packed"] = e.packed; d["nt"] = e.nt;
+    d["variant"] = e.variant; d["counters"] = e.counters; d["ws_bytes"] = e.ws_bytes; d["nt_hint"] = e.nt_hint;
+    d["qkv_cannot"] = e.qkv_cannot;
+    return d;
+  }, py::arg("M"), py::arg("N"), py::arg("K"), py::arg("fp8") = false, py::arg("glu") = false, py::arg("act") = 0,
+     py::arg("ws_bytes") = (int64_t)256 << 20, py::arg("nt_hint") = 0, py::arg("split_hint") = 0,
+     py::arg("tuned") = false, py::arg("has_out") = true, py::arg("partial_out") = false,
+     py::arg("has_packed") = false, py::arg("qkv_D") = 0, py::arg("neox") = false, py::arg("rope") = true,
+     py::arg("aligned") = true);
   m.def("gemm_tuned_set", &gemm_tuned_set);
   m.def("gemm_tuned_clear", &gemm_tuned_clear);
   m.def("gemm_reserve_streamk", &gemm_reserve_streamk);

@@ -20,12 +20,11 @@
 //  * gemm_big<F8> (prefill, M >= ~1K): 256x256 tile, 8 waves, 128 KiB double buffer whose K-tile
 //    t+2 is restaged while t is still being multiplied; F8 = W8A8 on the MX-fp8 matrix cores.
 //  * gemm_f8f8: tiled W8A8 for fp8 shapes too small for the 256x256 tile.
-// Split-K partial slabs never leave a call unless gemm_partial_slabs() says so (one source of
-// truth shared with the Python wrapper).
+// Which of them a call runs, with which tile, depth and split, and who finishes the output is resolved once per
+// call by csrc/gemm_plan.h (hint encoding, tile table, gemm_resolve); the launchers at the end of this file only
+// switch on the resolved plan, and gemm_partial_slabs() / gemm_plan() read the same plan for the Python wrapper.
 #include "common.h"
-
-#include <mutex>
-#include <unordered_map>
+#include "gemm_plan.h"
 
 // -------------------------------------------------------------------------------------------
 // helpers
@@ -1366,163 +1365,16 @@ __global__ __launch_bounds__(256) void gemm_f8f8_kernel(const unsigned char* __r
   }
 }
 
-// decode GEMM (csrc/gemm_dec.hip): hint tile bit 1024 (nt_hint bit 18), tile bits = the BN code, depth bits = ring
-// depth code (2 / 3 / 4 / 4 stages per wave), split_hint = K split over the grid (fp32 slabs for the consumer)
+static_assert(TBK == kGemmBK && TBK8 == kGemmBK8, "gemm_plan.h plans with the kernels' K steps");
+// csrc/gemm_dec.hip, csrc/gemm_mid.hip
 void launch_gemm_dec(int code, int depth, const bf16_t* X, int64_t ldx, const bf16_t* W, int64_t ldw,
                      const bf16_t* bias, bf16_t* Y, int64_t ldy, float* part, int M, int N, int K, int act, int glu,
                      int split, hipStream_t st, const QkvEpi* qe, int* cnt, bool packed = false);
-bool gemm_dec_bn(int code, int* bn);
-// the decode GEMM's in-launch combine (hint bit 256 with a split) fits the workspace: [tile][split][64 * bn] fp32
-static bool dec_combine_fits(int N, int tsel, int s, int64_t ws_bytes) {
-  int bn;
-  if (!(tsel & 256) || s <= 1 || !gemm_dec_bn(tsel & 15, &bn)) return false;
-  return (int64_t)((N + bn - 1) / bn) * s * 64 * bn * 4 <= ws_bytes;
-}
-static constexpr int kDecHint = 1024;
-// packed weights (hint tile bit 2048, nt_hint bit 19): the weight pointer is the panel-packed copy of W,
-// [ceil(N/16)][ceil(K/64)][16][64] bf16 with zeros past N and K (csrc/pack.hip, ops.hip.pack_panels). gemm_dec and the
-// 64-row gemm_mid tiles have the variant, for bf16 weights at M <= 64; the output is bit-identical to the same hint
-// without the bit. launch_gemm / launch_gemm_qkv take the packed copy as `w_packed` next to the row-major `w`: an
-// explicit hint with the bit and no packed copy, fp8 weights, M > 64 or a kernel without the variant throw; a TUNED
-// plan with the bit (gemm_tuned_set) called without a packed copy runs its row-major sibling - the same kernel, the
-// same bits - so a caller that never made a packed twin is not broken by another caller's tuning.
-static constexpr int kPackedHint = 2048;
-// gemm_dec and the gemm_mid tiles stage and zero their K tail in 16-byte chunks, so a hint that names one of them
-// takes any K % 8 == 0; every other kernel needs K % 16 == 0
-static bool k_ok(int K, int nt_hint) {
-  const int t = nt_hint >> 8;
-  return K % 16 == 0 || (K % 8 == 0 && !(nt_hint & 0xff) && !(t & 128) && ((t & kDecHint) || (t & 15) >= 7));
-}
-static const void* packed_select(const void* w, const void* w_packed, bool tuned, bool w_fp8, int M, int* nt_hint) {
-  if (!((*nt_hint >> 8) & kPackedHint)) return w;
-  if (!w_packed && tuned) {
-    *nt_hint &= ~(kPackedHint << 8);
-    return w;
-  }
-  if (!w_packed) throw std::runtime_error("gemm: the packed-weight hint (bit 2048) needs the packed copy of the weight");
-  if (w_fp8) throw std::runtime_error("gemm: packed weights are bf16 only (no fp8 variant)");
-  if (M > 64) throw std::runtime_error("gemm: packed weights serve M <= 64 only");
-  if (*nt_hint & 0xff) throw std::runtime_error("gemm: the streaming kernels have no packed-weight variant");
-  return w_packed;
-}
-static int dec_split(int M, int N, int K, int split_hint, int64_t ws_bytes) {
-  int s = std::max(1, std::min(split_hint, (K + 63) / 64));
-  if ((int64_t)s * M * N * 4 > ws_bytes) s = 1;
-  return s;
-}
-bool gemm_mid_dims(int tsel, int* bm, int* bn, int* threads);
 void launch_gemm_mid(int tsel, int depth, bool wnt, const bf16_t* X, int64_t ldx, const bf16_t* W, int64_t ldw,
                      const bf16_t* bias, bf16_t* Y, int64_t ldy, float* part, int M, int N, int K, int act, int glu,
                      int split, hipStream_t st, int* cnt = nullptr,
                      const QkvEpi* qe = nullptr, const float* xs = nullptr, const float* wsc = nullptr,
                      bool ilv = false, const unsigned char* asc = nullptr, bool packed = false);
-
-// tile: 1 = 128x128, 2 = 64x128, 3 = 64x64; ring depth 2-4; split-K over grid.y; 8-13: the gemm_mid tiles
-// (buffer-descriptor staging, csrc/gemm_mid.hip, fp8 MFMA variant; K % 128 == 0; ilv: its software-pipelined
-// k-loop, >= 3 stages)
-// MX-fp8 activations (gemm_mid tiles only): asc = e8m0 scales [M][K / 32] of xq (xs unused: nullptr), and mxq / mxs =
-// a SwiGLU output written as MX-fp8 instead of bf16 y (e4m3 [M][N / 2] with row stride ldy, scales [M][N / 64]; the
-// output tile must hold whole 32-output blocks, BN % 64 == 0, and finish in the launch: no split)
-// partial_out: a split plan without activation / GLU leaves its fp32 slabs [split, M, N] (scales applied, no
-// bias) in `workspace` for the consumer (rope_cache / add_norm sum them) and returns the split; else 0.
-int launch_gemm_f8f8(const void* xq, int64_t ldx, const void* xs, const void* wq, int64_t ldw, const void* wsc,
-                     const void* bias, void* y, int64_t ldy, int M, int N, int K, int act, bool glu, int tile,
-                     int depth, int split, void* workspace, int64_t ws_bytes, hipStream_t st, bool partial_out,
-                     bool ilv, void* mxq, void* mxs, const void* asc) {
-  if (M == 0 || N == 0) return 0;
-  if (K % 16) throw std::runtime_error("gemm_f8f8: K must be a multiple of 16");
-  if (glu && (N % 32)) throw std::runtime_error("gemm_f8f8: glu needs N % 32 == 0");
-  if (!y && !partial_out && !mxq) throw std::runtime_error("gemm_f8f8: output required");
-  int bm = tile == 1 ? 128 : 64, bn = tile == 3 ? 64 : 128, thr = 256;
-  const bool mid = tile >= 7 && tile <= 15;
-  if (mid) {
-    if (K % 128) throw std::runtime_error("gemm_f8f8: gemm_mid tiles need K % 128 == 0");
-    gemm_mid_dims(tile, &bm, &bn, &thr);
-  }
-  if ((asc || mxq) && !mid) throw std::runtime_error("gemm_f8f8: MX-fp8 activations need a gemm_mid tile (7-15)");
-  if (asc && (xs || K % 128)) throw std::runtime_error("gemm_f8f8: MX scales replace xs; K % 128 == 0");
-  if (mxq && (!mxs || !glu || bn % 64 || N % 128 || ldy != N / 2 || partial_out))
-    throw std::runtime_error("gemm_f8f8: MX output needs SwiGLU, BN % 64 == 0, N % 128 == 0, dense rows, no slabs");
-  const int tiles = ((M + bm - 1) / bm) * ((N + bn - 1) / bn);
-  const int nk = (K + TBK8 - 1) / TBK8;
-  if (tile == 4 || (tile == 0 && K % 128 == 0 && ((M + 255) / 256) * ((N + 255) / 256) >= 192)) {
-    if (K % 128) throw std::runtime_error("gemm_f8f8: the 256x256 tile needs K % 128 == 0");
-    gemm_big_kernel<true><<<((M + 255) / 256) * ((N + 255) / 256), 512, 0, st>>>(
-        xq, ldx, wq, ldw, (const bf16_t*)bias, (bf16_t*)y, ldy, M, N, K, act, glu ? 1 : 0, (const float*)xs,
-        (const float*)wsc, g_big_group_m);
-    HIP_CHECK_LAUNCH();
-    return 0;
-  }
-  if (tile == 0) {  // auto: 128x128 when it fills the chip, else 64x128 / 64x64, split to >= ~256 WGs
-    tile = ((M + 127) / 128) * ((N + 127) / 128) >= 240 ? 1 : (((M + 63) / 64) * ((N + 127) / 128) >= 240 ? 2 : 3);
-    return launch_gemm_f8f8(xq, ldx, xs, wq, ldw, wsc, bias, y, ldy, M, N, K, act, glu, tile, depth, split, workspace,
-                            ws_bytes, st, partial_out, ilv, mxq, mxs, asc);
-  }
-  if (split <= 0) {
-    split = 1;
-    while (tiles * split * 2 <= 512 && nk / (2 * split) >= 4 && split < 8) split *= 2;
-  }
-  split = std::max(1, std::min(split, nk));
-  if ((int64_t)split * M * N * 4 > ws_bytes) split = 1;
-  if (mxq && split > 1) throw std::runtime_error("gemm_f8f8: an MX-fp8 SwiGLU output cannot be split over K");
-  float* part = split > 1 ? (float*)workspace : nullptr;
-  const int act_k = split > 1 ? 0 : act, g = glu ? 1 : 0, glu_k = split > 1 ? 0 : g;
-  if (depth <= 0) depth = tile == 1 ? 3 : 4;
-  if (tile == 1 && depth > 3) depth = 3;
-  dim3 grid(tiles, split);
-  auto A = (const unsigned char*)xq;
-  auto Bw = (const unsigned char*)wq;
-  auto XS = (const float*)xs;
-  auto WSc = (const float*)wsc;
-  auto Bi = (const bf16_t*)bias;
-  auto Y = (bf16_t*)y;
-#define LF(BM_, BN_, NS_) \
-  gemm_f8f8_kernel<BM_, BN_, NS_><<<grid, 256, 0, st>>>(A, ldx, XS, Bw, ldw, WSc, Bi, Y, ldy, part, M, N, K, act_k, glu_k)
-  if (mid) {
-    QkvEpi mx{};
-    mx.mxq = (unsigned char*)mxq;
-    mx.mxs = (unsigned char*)mxs;
-    launch_gemm_mid(tile, depth, M <= bm, (const bf16_t*)xq, ldx, (const bf16_t*)wq, ldw, Bi, Y, ldy, part, M, N, K,
-                    act_k, glu_k, split, st, nullptr, mxq ? &mx : nullptr, XS, WSc, ilv,
-                    (const unsigned char*)asc);
-  } else if (tile == 1) {
-    if (depth >= 3) LF(128, 128, 3); else LF(128, 128, 2);
-  } else if (tile == 2) {
-    if (depth >= 4) LF(64, 128, 4); else if (depth == 3) LF(64, 128, 3); else LF(64, 128, 2);
-  } else {
-    if (depth >= 4) LF(64, 64, 4); else if (depth == 3) LF(64, 64, 3); else LF(64, 64, 2);
-  }
-#undef LF
-  HIP_CHECK_LAUNCH();
-  if (split > 1 && partial_out && !glu && act == 0) return split;
-  if (split > 1) {
-    if (!y) throw std::runtime_error("gemm_f8f8: output required");
-    const int nout = glu ? N / 2 : N;
-    dim3 rgrid(std::min((nout + 255) / 256, 64), M);
-    splitk_reduce_kernel<<<rgrid, 256, 0, st>>>(part, split, M, N, Bi, Y, ldy, act, g);
-    HIP_CHECK_LAUNCH();
-  }
-  return 0;
-}
-
-// the split a W8A8 call with these arguments leaves as slabs under partial_out (0 = finished output)
-int gemm_f8f8_partial_slabs(int M, int N, int K, bool glu, int act, int tile, int split, int64_t ws_bytes) {
-  if (M == 0 || N == 0 || glu || act != 0) return 0;
-  if (tile == 4 || (tile == 0 && K % 128 == 0 && ((M + 255) / 256) * ((N + 255) / 256) >= 192)) return 0;
-  if (tile == 0)
-    tile = ((M + 127) / 128) * ((N + 127) / 128) >= 240 ? 1 : (((M + 63) / 64) * ((N + 127) / 128) >= 240 ? 2 : 3);
-  int bm = tile == 1 ? 128 : 64, bn = tile == 3 ? 64 : 128, thr;
-  if (tile >= 7 && tile <= 15) gemm_mid_dims(tile, &bm, &bn, &thr);
-  const int tiles = ((M + bm - 1) / bm) * ((N + bn - 1) / bn);
-  const int nk = (K + TBK8 - 1) / TBK8;
-  if (split <= 0) {
-    split = 1;
-    while (tiles * split * 2 <= 512 && nk / (2 * split) >= 4 && split < 8) split *= 2;
-  }
-  split = std::max(1, std::min(split, nk));
-  if ((int64_t)split * M * N * 4 > ws_bytes) split = 1;
-  return split > 1 ? split : 0;
-}
 
 // -------------------------------------------------------------------------------------------
 // host dispatch
@@ -1573,194 +1425,6 @@ static void launch_stream(int variant, int mt, int nt, const bf16_t* X, int64_t 
     }
   }
 #undef LS
-}
-
-// Tile/split choice for the streaming kernel: columns per workgroup and K splits such that the
-// grid reaches ~2 workgroups per CU (256 CUs) without splitting K below 4 chunks per slice.
-void gemm_stream_plan(int M, int N, int K, int* nt_out, int* splitk_out) {
-  int nt = (N >= 16384) ? 2 : 1;
-  const int nblk = (N + 64 * nt - 1) / (64 * nt);
-  const int kc = M > 64 ? 128 : 256;
-  const int nck = (K + kc - 1) / kc;
-  // measured (bench/gemm_bench.py --sweep, Llama-2-7B shapes): M <= 16 likes ~3 workgroups per
-  // CU, larger M ~1 per CU (its X tile already costs LDS); N alone filling the chip -> no split
-  const int target = nblk >= 256 ? nblk : (M <= 16 ? 768 : 256);
-  int s = 1;
-  while (nblk * s < target && s < 16 && nck / (2 * s) >= 4) s *= 2;
-  *nt_out = nt;
-  *splitk_out = s;
-}
-
-int gemm_skinny_splitk(int M, int N, int K) {
-  int nt, s;
-  gemm_stream_plan(M, N, K, &nt, &s);
-  return s;
-}
-
-int launch_tiled(const bf16_t* X, int64_t ldx, const void* W, int64_t ldw, const bf16_t* B, bf16_t* Y, int64_t ldy,
-                 int M, int N, int K, int act, int g, int tsel, int split_hint, void* workspace, int64_t ws_bytes,
-                 bool partial_out, hipStream_t st, const float* wscale = nullptr, const QkvEpi* qe = nullptr);
-
-int gemm_partial_slabs(int M, int N, int K, bool w_fp8, bool glu, int act, int nt_hint, int split_hint,
-                       int64_t ws_bytes);
-void gemm_tiled_plan(int M, int N, int K, int* tsel_io, int* split_io, bool glu);
-void gemm_stream_plan(int M, int N, int K, int* nt_out, int* splitk_out);
-
-// Returns the number of fp32 partial slabs [S, M, N] left in `workspace` (partial_out and the
-// planner chose split-K: the consumer - add_norm - reduces them and adds `bias`), or 0 when Y
-// holds the finished bf16 output.
-// Autotuned plans: (M, N, K, glu, fp8) -> (nt_hint, split) measured by llmss_amd/ops/autotune.py
-// for the shapes an engine will actually run (decode batch buckets x layer GEMMs). Consulted by
-// every call without explicit hints and by gemm_plan, so split-K partial fusion stays consistent.
-namespace {
-std::mutex g_tuned_mu;
-std::unordered_map<uint64_t, std::pair<int, int>> g_tuned;
-// kind: 0 = bf16 [N, K] weights, 1 = fp8 weights, 3 = QKV
-// RoPE / KV-write epilogue (launch_gemm_qkv)
-uint64_t tune_key(int M, int N, int K, bool glu, int kind) {
-  return ((uint64_t)(kind & 7) << 61) | ((uint64_t)(M & 0x7FFFF) << 42) | ((uint64_t)N << 22) |
-         ((uint64_t)K << 2) | (glu ? 2u : 0u) | (kind == 1 ? 1u : 0u);
-}
-}  // namespace
-
-void gemm_tuned_set(int M, int N, int K, bool glu, int kind, int nt_hint, int split) {
-  std::lock_guard<std::mutex> lk(g_tuned_mu);
-  g_tuned[tune_key(M, N, K, glu, kind)] = {nt_hint, split};
-}
-void gemm_tuned_clear() {
-  std::lock_guard<std::mutex> lk(g_tuned_mu);
-  g_tuned.clear();
-}
-bool gemm_tuned_get(int M, int N, int K, bool glu, int kind, int* nt_hint, int* split) {
-  std::lock_guard<std::mutex> lk(g_tuned_mu);
-  auto it = g_tuned.find(tune_key(M, N, K, glu, kind));
-  if (it == g_tuned.end()) return false;
-  *nt_hint = it->second.first;
-  *split = it->second.second;
-  return true;
-}
-
-int launch_gemm(const void* x, int64_t ldx, const void* w, int64_t ldw, bool w_fp8, const void* w_scale,
-                const void* bias, void* y, int64_t ldy, int M, int N, int K, int act, bool glu, void* workspace,
-                int64_t ws_bytes, int nt_hint, int split_hint, bool partial_out, hipStream_t st,
-                const void* w_packed) {
-  if (M == 0 || N == 0) return 0;
-  bool tuned = false;
-  if (nt_hint == 0 && split_hint == 0) tuned = gemm_tuned_get(M, N, K, glu, w_fp8 ? 1 : 0, &nt_hint, &split_hint);
-  w = packed_select(w, w_packed, tuned, w_fp8, M, &nt_hint);
-  if (!y && (!partial_out || gemm_partial_slabs(M, N, K, w_fp8, glu, act, nt_hint, split_hint, ws_bytes) == 0))
-    throw std::runtime_error("gemm: this configuration writes the output, but no output buffer was given");
-  if (!k_ok(K, nt_hint)) throw std::runtime_error("gemm: K must be a multiple of 16 (of 8 on gemm_dec / gemm_mid hints)");
-  if (glu && (N % 32)) throw std::runtime_error("gemm: glu needs N % 32 == 0");
-  auto X = (const bf16_t*)x;
-  auto B = (const bf16_t*)bias;
-  auto Y = (bf16_t*)y;
-  auto WS = (const float*)w_scale;
-  const int g = glu ? 1 : 0;
-  // weight-streaming kernel: M <= 16, explicit stream hints, and fp8 prefill panels; fp8 decode
-  // (16 < M <= 128) runs the tiled kernel with fp8 weight tiles (W8A16)
-  const int tiled_hint = nt_hint >> 8;
-  const bool stream = (nt_hint & 0xff) || (!tiled_hint && (M <= 16 || (w_fp8 && M > 128)));
-  if (stream) {
-    if (M > 128) {  // fp8 weights with many rows (prefill): 128-row panels through the streaming kernel
-      for (int m0 = 0; m0 < M; m0 += 128) {
-        const int mm = std::min(128, M - m0);
-        launch_gemm((const bf16_t*)x + m0 * ldx, ldx, w, ldw, w_fp8, w_scale, bias, (bf16_t*)y + m0 * ldy, ldy, mm, N,
-                    K, act, glu, workspace, ws_bytes, nt_hint, split_hint, false, st, nullptr);
-      }
-      return 0;
-    }
-    int nt, splitk;
-    gemm_stream_plan(M, N, K, &nt, &splitk);
-    // nt_hint = nt + 16 * variant (variant 1: LDS-DMA X staging, 2: register-staged X + W ring)
-    int variant = ((nt_hint >> 4) & 15) ? ((nt_hint >> 4) & 15) : 2;
-    nt_hint &= 15;
-    if (nt_hint > 0) nt = nt_hint;
-    if (split_hint > 0) splitk = split_hint;
-    if (glu && nt < 2) nt = 2;  // the SwiGLU epilogue pairs (gate, up) 16-column tiles inside a wave
-    if ((int64_t)splitk * M * N * 4 > ws_bytes) splitk = 1;
-    float* part = splitk > 1 ? (float*)workspace : nullptr;
-    const int mt = (M + 15) / 16;
-    const int act_k = splitk > 1 ? 0 : act, glu_k = splitk > 1 ? 0 : g;
-    if (w_fp8) launch_stream<true>(variant, mt, nt, X, ldx, w, ldw, WS, B, Y, ldy, part, M, N, K, act_k, glu_k, splitk, st);
-    else launch_stream<false>(variant, mt, nt, X, ldx, w, ldw, nullptr, B, Y, ldy, part, M, N, K, act_k, glu_k, splitk, st);
-    if (splitk > 1 && partial_out && !glu && act == 0) return splitk;
-    if (splitk > 1) {
-      const int nout = glu ? N / 2 : N;
-      dim3 grid(std::min((nout + 255) / 256, 64), M);
-      splitk_reduce_kernel<<<grid, 256, 0, st>>>(part, splitk, M, N, B, Y, ldy, act, g);
-      HIP_CHECK_LAUNCH();
-    }
-    return 0;
-  }
-  return launch_tiled(X, ldx, w, ldw, B, Y, ldy, M, N, K, act, g, nt_hint >> 8, split_hint, workspace,
-                      ws_bytes, partial_out, st, w_fp8 ? WS : nullptr);
-}
-
-// Tiled-path plan. Tile: 64 rows for M <= 64 (64x64, or 64x128 when 64x64 gives > 256 tiles),
-// else 128x128. K is split until the grid holds ~3 (64-row tiles) or ~1.5 (128x128) workgroups
-// per CU, keeping >= 512 k per slice. Measured on the Llama-2-7B shapes at M = 64..512
-// (bench/gemm_bench.py --sweep): within ~5% of the best (tile, split) of the sweep everywhere.
-static int tiles_of(int M, int N, int bm, int bn) { return ((M + bm - 1) / bm) * ((N + bn - 1) / bn); }
-// tsel: 1 = 128x128, 2 = 64x128, 3 = 64x64 (4 waves); 5 = 256x128, 6 = 256x64 (8 waves, 1 WG/CU);
-// 4 = the big-tile kernel
-bool gemm_mid_dims(int tsel, int* bm, int* bn, int* threads);
-
-// tsel 8-12: gemm_mid (gemm_mid.hip: buffer-descriptor staging, 128x128 / 256x128 / 64x256 / 64x128 / 128x256)
-static int tile_dims(int tsel, int* bm, int* bn) {
-  int thr;
-  if (gemm_mid_dims(tsel, bm, bn, &thr)) return 0;
-  *bm = tsel >= 5 ? 256 : (tsel == 1 ? 128 : 64);
-  *bn = (tsel == 3 || tsel == 6) ? 64 : 128;
-  return 0;
-}
-void gemm_tiled_plan(int M, int N, int K, int* tsel_io, int* split_io, bool glu) {
-  int tsel = *tsel_io;
-  // SwiGLU output cannot be folded into the next kernel, so a split would cost its own reduce
-  // launch: with >= 256 64x64 tiles, no split (measured equal or better at M <= 128)
-  if (tsel == 0 && glu && M <= 128 && tiles_of(M, N, 64, 64) >= 256 && *split_io <= 0) {
-    *tsel_io = 3 | 16;
-    *split_io = 1;
-    return;
-  }
-  if (tsel == 0) {
-    if (tiles_of(M, N, 256, 256) >= 192) tsel = 4;
-    else tsel = M <= 64 ? (tiles_of(M, N, 64, 64) > 256 ? 2 : 3) : 1;
-  }
-  int hint_bits = tsel & ~15;
-  tsel &= 15;
-  if (tsel >= 5) hint_bits &= ~128;  // no stream-K variant of the 8-wave tiles
-  if (hint_bits & 128) {  // stream-K: output is final (no slabs); split_io carries workgroups per CU
-    *tsel_io = tsel | hint_bits;
-    if (*split_io <= 0) *split_io = 2;
-    return;
-  }
-  if (tsel == 4) {  // big-tile kernel: no split-K, no stage option
-    *tsel_io = 4;
-    *split_io = 1;
-    return;
-  }
-  int bm, bn;
-  tile_dims(tsel, &bm, &bn);
-  const int nt = tiles_of(M, N, bm, bn);
-  int s = *split_io;
-  if (s <= 0) {
-    const int bound = bm == 64 ? 800 : (bm == 128 ? 537 : 300);
-    s = 1;
-    while (nt * s * 2 <= bound && s < 8 && K / (2 * s) >= 512) s *= 2;
-  }
-  s = std::max(1, std::min(s, (K + TBK - 1) / TBK));
-  // 3-stage LDS ring when the grid is too small for block-level latency hiding (measured: o/down
-  // projections and the LM head at M <= 128 gain 10-20%; wide grids lose occupancy to its LDS)
-  if (*tsel_io == 0 && nt * s <= (bm == 64 ? 600 : 256)) tsel |= 16;
-  *tsel_io = tsel | hint_bits;
-  *split_io = s;
-}
-
-static bool wnt_ok(int tsel_raw, int M, int tsel) {
-  int bm, bn;
-  tile_dims(tsel & 15, &bm, &bn);
-  return !(tsel_raw & 64) && M <= bm;
 }
 
 // per-tile arrival counters of the stream-K and split-K combines, one buffer per device: zeroed
@@ -1817,224 +1481,136 @@ void gemm_reserve_streamk(int n) {
   (void)zero_page();
 }
 
-static bool launch_streamk(const bf16_t* X, int64_t ldx, const bf16_t* W, int64_t ldw, const bf16_t* B, bf16_t* Y,
-                           int64_t ldy, int M, int N, int K, int act, int g, int tsel, int ns, int per_cu,
-                           void* workspace, int64_t ws_bytes, bool wnt, hipStream_t st) {
-  int bm, bn;
-  tile_dims(tsel, &bm, &bn);
-  if (tsel == 1 && ns > 3) ns = 3;
-  if (tsel == 2 && ns > 4) ns = 4;
-  if (ns == 6) ns = 4;
-  const int tiles = tiles_of(M, N, bm, bn), nk = (K + TBK - 1) / TBK;
-  const int64_t U = (int64_t)tiles * nk;
-  if (U >= (1LL << 31)) return false;
-  const int G = (int)std::min<int64_t>(U, 256LL * std::max(1, std::min(per_cu, 8)));
-  const int64_t per = U / G;  // >= 1
-  const int maxseg = (int)std::min<int64_t>(G, (nk + per - 1) / per + 1);
-  if ((int64_t)tiles * maxseg * bm * bn * 4 > ws_bytes) return false;
-  int* cnt = sk_counters(tiles);
-  float* part = (float*)workspace;
-#define SK(BM_, BN_, NS_)                                                                                          \
-  do {                                                                                                             \
-    if (wnt)                                                                                                       \
-      gemm_streamk_kernel<BM_, BN_, NS_, true><<<G, 256, 0, st>>>(X, ldx, W, ldw, B, Y, ldy, part, cnt, maxseg, M, N, \
-                                                                   K, act, g);                                     \
-    else                                                                                                           \
-      gemm_streamk_kernel<BM_, BN_, NS_, false><<<G, 256, 0, st>>>(X, ldx, W, ldw, B, Y, ldy, part, cnt, maxseg, M, \
-                                                                    N, K, act, g);                                 \
-  } while (0)
-  if (tsel == 1) {
-    if (ns == 3) SK(128, 128, 3); else SK(128, 128, 2);
-  } else if (tsel == 2) {
-    if (ns == 4) SK(64, 128, 4); else if (ns == 3) SK(64, 128, 3); else SK(64, 128, 2);
-  } else {
-    if (ns == 4) SK(64, 64, 4); else if (ns == 3) SK(64, 64, 3); else SK(64, 64, 2);
-  }
-#undef SK
-  HIP_CHECK_LAUNCH();
-  return true;
+// the branch of a run-time flag as a compile-time one: f(std::true_type) or f(std::false_type)
+template <class F>
+static void pick(bool b, F&& f) {
+  if (b) f(std::true_type{}); else f(std::false_type{});
 }
+#define PICKED(T_) decltype(T_)::value
 
-int launch_tiled(const bf16_t* X, int64_t ldx, const void* W, int64_t ldw, const bf16_t* B, bf16_t* Y, int64_t ldy,
-                 int M, int N, int K, int act, int g, int tsel, int split_hint, void* workspace, int64_t ws_bytes,
-                 bool partial_out, hipStream_t st, const float* wscale, const QkvEpi* qe) {
-  const QkvEpi qv = qe ? *qe : QkvEpi{};
-  const int tsel_raw = tsel;
-  int s = split_hint;
-  const bool f8 = wscale != nullptr;  // fp8-e4m3 weights (W8A16): half the weight bytes of a decode step
-  const bool packed = (tsel & kPackedHint) != 0;  // W is the panel-packed copy (kPackedHint)
-  if (packed && (f8 || M > 64)) throw std::runtime_error("gemm: packed weights serve bf16 weights at M <= 64 only");
-  if (tsel & kDecHint) {  // K split over the waves (gemm_dec.hip), M <= 64, bf16 weights
-    if (f8) throw std::runtime_error("gemm_dec: bf16 weights only");
-    s = dec_split(M, N, K, split_hint, ws_bytes);
-    if (s > 1 && Y && dec_combine_fits(N, tsel, s, ws_bytes)) {  // split-K combined in the launch: finished Y
-      int bn;
-      gemm_dec_bn(tsel & 15, &bn);
-      static constexpr int kDecDepthC[4] = {2, 3, 4, 4};
-      launch_gemm_dec(tsel & 15, kDecDepthC[(tsel >> 4) & 3], X, ldx, (const bf16_t*)W, ldw, B, Y, ldy,
-                      (float*)workspace, M, N, K, act, g, s, st, qe, sk_counters((N + bn - 1) / bn), packed);
-      return 0;
-    }
-    if (qe && s > 1) throw std::runtime_error("gemm_dec: the QKV epilogue needs an unsplit or in-launch-combined plan");
-    static constexpr int kDecDepth[4] = {2, 3, 4, 4};
-    float* part = s > 1 ? (float*)workspace : nullptr;
-    launch_gemm_dec(tsel & 15, kDecDepth[(tsel >> 4) & 3], X, ldx, (const bf16_t*)W, ldw, B, Y, ldy, part, M, N, K,
-                    s > 1 ? 0 : act, s > 1 ? 0 : g, s, st, qe, nullptr, packed);
-    if (s > 1 && partial_out && !g && act == 0) return s;
-    if (s > 1) {
-      const int nout = g ? N / 2 : N;
-      dim3 rgrid(std::min((nout + 255) / 256, 64), M);
-      splitk_reduce_kernel<<<rgrid, 256, 0, st>>>(part, s, M, N, B, Y, ldy, act, g);
-      HIP_CHECK_LAUNCH();
-    }
-    return 0;
-  }
-  if (f8 && (tsel & 15) >= 5) tsel = (tsel & ~15) | 1;  // 8-wave and mid tiles are bf16-only
-  gemm_tiled_plan(M, N, K, &tsel, &s, g != 0);
-  static constexpr int kDepth[4] = {2, 3, 4, 6};
-  int ns = kDepth[(tsel >> 4) & 3];  // LDS ring depth (hint bits 4-5); bit 6: default-policy weights
-  tsel &= 15;
-  if (packed && (tsel < 7 || (tsel_raw & 128)))
-    throw std::runtime_error("gemm: this kernel has no packed-weight variant (gemm_dec and 64-row gemm_mid tiles only)");
-  // the ping-pong kernel's zero-page K tail works on 8-element chunks and its LDS-DMA rows need 16-B aligned
-  // strides: anything else runs on the 128x128 tile (tuned hints and C++ callers included, not just linear())
-  if (tsel == 4 && (K % 8 || ldx % 8 || ldw % 8)) tsel = 1;
-  if ((tsel == 1 || tsel == 5) && ns > 3) ns = 3;  // 128x128 / 256x128 x 4 stages exceed the 160 KiB LDS
-  if ((tsel == 2 || tsel == 6) && ns > 4) ns = 4;
-  if (f8 && tsel == 4) tsel = 1;
-  if (tsel == 4) {
-    if (K & 63)
-      gemm_pp_kernel<true><<<tiles_of(M, N, 256, 256), 512, 0, st>>>(X, ldx, (const bf16_t*)W, ldw, B, Y, ldy, M, N, K,
-                                                                     act, g, g_big_group_m, zero_page());
-    else
-      gemm_pp_kernel<false><<<tiles_of(M, N, 256, 256), 512, 0, st>>>(X, ldx, (const bf16_t*)W, ldw, B, Y, ldy, M, N, K,
-                                                                      act, g, g_big_group_m, nullptr);
-    HIP_CHECK_LAUNCH();
-    return 0;
-  }
-  if ((tsel_raw & 128) && !f8 && tsel < 5) {
-    if (launch_streamk(X, ldx, (const bf16_t*)W, ldw, B, Y, ldy, M, N, K, act, g, tsel, ns, s, workspace, ws_bytes,
-                       wnt_ok(tsel_raw, M, tsel), st))
-      return 0;
-    s = 1;  // workspace too small for the partial tiles: plain tiled launch
-  }
-  int bm, bn;
-  tile_dims(tsel, &bm, &bn);
-  const int nt = tiles_of(M, N, bm, bn);
-  // hint bit 8: split-K slices combine in-launch (last arriver per tile, common.h splitk_combine):
-  // slabs [tile][S][bm*bn] in the workspace, finished bf16 output, no reduce launch
-  int* cnt = nullptr;
-  if ((tsel_raw & 256) && s > 1 && (int64_t)nt * s * bm * bn * 4 <= ws_bytes && Y) cnt = sk_counters(nt);
-  if (!cnt && (int64_t)s * M * N * 4 > ws_bytes) s = 1;
-  if (qe && (s > 1 && !cnt)) throw std::runtime_error("gemm: the QKV epilogue needs an unsplit or in-launch-combined plan");
-  float* part = s > 1 ? (float*)workspace : nullptr;
-  const int act_k = s > 1 && !cnt ? 0 : act, glu_k = s > 1 && !cnt ? 0 : g;
-  dim3 grid(nt, s);
-  if (tsel >= 7 && tsel <= 15) {  // gemm_mid tiles (7, 8-15)
-    launch_gemm_mid(tsel, ns, wnt_ok(tsel_raw, M, tsel), X, ldx, (const bf16_t*)W, ldw, B, Y, ldy, part, M, N, K,
-                    act_k, glu_k, s, st, cnt, qe, nullptr, nullptr, (tsel_raw & 512) != 0, nullptr, packed);
-    if (cnt) return 0;
-    if (s > 1 && partial_out && !g && act == 0) return s;
-    if (s > 1) {
-      const int nout = g ? N / 2 : N;
-      dim3 rgrid(std::min((nout + 255) / 256, 64), M);
-      splitk_reduce_kernel<<<rgrid, 256, 0, st>>>(part, s, M, N, B, Y, ldy, act, g);
-      HIP_CHECK_LAUNCH();
-    }
-    return 0;
-  }
-  // non-temporal weight staging when every weight tile is read by exactly one workgroup row
-  const bool wnt = wnt_ok(tsel_raw, M, tsel);
-  if (tsel >= 5) {  // 8-wave tiles (bf16 weights)
-#define LT8(BM_, BN_, NS_)                                                                                          \
-  do {                                                                                                             \
-    if (wnt)                                                                                                       \
-      gemm_tiled_kernel<BM_, BN_, NS_, true, false, 8><<<grid, 512, 0, st>>>(X, ldx, W, ldw, B, Y, ldy, part, M, N, K, \
-                                                                             act_k, glu_k, nullptr, cnt, qv);      \
-    else                                                                                                           \
-      gemm_tiled_kernel<BM_, BN_, NS_, false, false, 8><<<grid, 512, 0, st>>>(X, ldx, W, ldw, B, Y, ldy, part, M, N,  \
-                                                                              K, act_k, glu_k, nullptr, cnt, qv);  \
-  } while (0)
-    if (tsel == 5) {
-      if (ns == 3) LT8(256, 128, 3); else LT8(256, 128, 2);
-    } else {
-      if (ns == 4) LT8(256, 64, 4); else if (ns == 3) LT8(256, 64, 3); else LT8(256, 64, 2);
-    }
-#undef LT8
-  } else {
-#define LT1(BM_, BN_, NS_, WNT_, F8_)                                                                              \
-  gemm_tiled_kernel<BM_, BN_, NS_, WNT_, F8_><<<grid, 256, 0, st>>>(X, ldx, W, ldw, B, Y, ldy, part, M, N, K, act_k,  \
-                                                                    glu_k, wscale, cnt, qv)
-#define LT(BM_, BN_, NS_)                                                                                          \
-  do {                                                                                                             \
-    if (f8) {                                                                                                      \
-      if (wnt) LT1(BM_, BN_, NS_, true, true); else LT1(BM_, BN_, NS_, false, true);                              \
-    } else {                                                                                                       \
-      if (wnt) LT1(BM_, BN_, NS_, true, false); else LT1(BM_, BN_, NS_, false, false);                            \
-    }                                                                                                              \
-  } while (0)
-  if (ns == 3) {
-    if (tsel == 1) LT(128, 128, 3); else if (tsel == 2) LT(64, 128, 3); else LT(64, 64, 3);
-  } else if (ns == 4) {
-    if (tsel == 2) LT(64, 128, 4); else LT(64, 64, 4);
-  } else if (ns == 6) {
-    LT(64, 64, 6);
-  } else {
-    if (tsel == 1) LT(128, 128, 2); else if (tsel == 2) LT(64, 128, 2); else LT(64, 64, 2);
-  }
-  }
-#undef LT
-#undef LT1
-  HIP_CHECK_LAUNCH();
-  if (cnt) return 0;
-  if (s > 1 && partial_out && !g && act == 0) return s;
-  if (s > 1) {
+// what is left to do after a plan's kernel: nothing, slabs for the consumer (returns their count), or the reduce
+static int gemm_finish(const GemmExec& e, float* part, int M, int N, const bf16_t* B, bf16_t* Y, int64_t ldy, int act,
+                       int g, hipStream_t st) {
+  if (e.finish == GemmFinish::kSlabs) return e.split;
+  if (e.finish == GemmFinish::kReduce) {
     const int nout = g ? N / 2 : N;
-    dim3 rgrid(std::min((nout + 255) / 256, 64), M);
-    splitk_reduce_kernel<<<rgrid, 256, 0, st>>>(part, s, M, N, B, Y, ldy, act, g);
+    dim3 grid(std::min((nout + 255) / 256, 64), M);
+    splitk_reduce_kernel<<<grid, 256, 0, st>>>(part, e.split, M, N, B, Y, ldy, act, g);
     HIP_CHECK_LAUNCH();
   }
   return 0;
 }
 
-// Number of fp32 partial slabs launch_gemm(..., partial_out=true) leaves for these hints, or 0 if
-// that call writes the finished output (stream-K, fp8 prefill panels, act / glu epilogues, no
-// split). The Python wrapper allocates Y exactly when this returns 0 - one source of truth.
-int gemm_partial_slabs(int M, int N, int K, bool w_fp8, bool glu, int act, int nt_hint, int split_hint,
-                       int64_t ws_bytes) {
-  if (M == 0 || N == 0 || glu || act != 0) return 0;
-  if (nt_hint == 0 && split_hint == 0) gemm_tuned_get(M, N, K, glu, w_fp8 ? 1 : 0, &nt_hint, &split_hint);
-  const int tiled_hint = nt_hint >> 8;
-  const bool stream = (nt_hint & 0xff) || (!tiled_hint && (M <= 16 || (w_fp8 && M > 128)));
-  int s;
-  if (stream) {
-    if (M > 128) return 0;  // 128-row panels, each finished in place
-    int nt;
-    gemm_stream_plan(M, N, K, &nt, &s);
-    if (split_hint > 0) s = split_hint;
-  } else {
-    int tsel = tiled_hint;
-    if (tsel & kDecHint) {
-      if (w_fp8) return 0;  // rejected at launch
-      s = dec_split(M, N, K, split_hint, ws_bytes);
-      if (dec_combine_fits(N, tsel, s, ws_bytes)) return 0;  // combined in the launch
-      return s > 1 ? s : 0;
+// Launches a resolved bf16-activation plan (W: the weight pointer the plan reads, packed or row-major; wscale:
+// fp8-e4m3 weights, W8A16). Returns the number of fp32 partial slabs [S, M, N] left in `workspace`, or 0 when Y
+// holds the finished bf16 output.
+static int launch_plan(const GemmExec& e, const bf16_t* X, int64_t ldx, const void* W, int64_t ldw, const float* wscale,
+                       const bf16_t* B, bf16_t* Y, int64_t ldy, int M, int N, int K, int act, int g, void* workspace,
+                       hipStream_t st, const QkvEpi* qe = nullptr) {
+  const QkvEpi qv = qe ? *qe : QkvEpi{};
+  const bool f8 = wscale != nullptr, wnt = e.wnt;
+  const int s = e.split, ns = e.depth, tsel = e.tile;
+  float* part = s > 1 || e.family == GemmFamily::kStreamK ? (float*)workspace : nullptr;
+  const int act_k = e.split_out() ? 0 : act, glu_k = e.split_out() ? 0 : g;  // a split-out plan's epilogue comes later
+  int* cnt = e.counters ? sk_counters(e.counters) : nullptr;
+  const dim3 grid(e.bm ? tiles_of(M, N, e.bm, e.bn) : 0, s);
+  switch (e.family) {
+    case GemmFamily::kStream:
+      pick(f8, [&](auto F8) {
+        launch_stream<PICKED(F8)>(e.variant, (M + 15) / 16, e.nt, X, ldx, W, ldw, wscale, B, Y, ldy, part, M, N, K,
+                                  act_k, glu_k, s, st);
+      });
+      break;
+    case GemmFamily::kDec:
+      launch_gemm_dec(tsel, ns, X, ldx, (const bf16_t*)W, ldw, B, Y, ldy, part, M, N, K, act_k, glu_k, s, st, qe, cnt,
+                      e.packed);
+      break;
+    case GemmFamily::kMid:
+      launch_gemm_mid(tsel, ns, wnt, X, ldx, (const bf16_t*)W, ldw, B, Y, ldy, part, M, N, K, act_k, glu_k, s, st,
+                      cnt, qe, nullptr, nullptr, e.ilv, nullptr, e.packed);
+      break;
+    case GemmFamily::kPingPong:
+      pick((K & 63) != 0, [&](auto TAIL) {  // a partial last K-tile reads the zero page
+        gemm_pp_kernel<PICKED(TAIL)><<<grid.x, 512, 0, st>>>(X, ldx, (const bf16_t*)W, ldw, B, Y, ldy, M, N, K, act, g,
+                                                             g_big_group_m, PICKED(TAIL) ? zero_page() : nullptr);
+      });
+      break;
+    case GemmFamily::kStreamK: {
+      const int G = e.sk_grid, maxseg = e.sk_maxseg;
+      auto Wb = (const bf16_t*)W;
+#define SK(BM_, BN_, NS_)                                                                                        \
+  pick(wnt, [&](auto WNT) {                                                                                      \
+    gemm_streamk_kernel<BM_, BN_, NS_, PICKED(WNT)><<<G, 256, 0, st>>>(X, ldx, Wb, ldw, B, Y, ldy, part, cnt, maxseg, \
+                                                                        M, N, K, act, g);                        \
+  })
+      if (tsel == 1) {
+        if (ns == 3) SK(128, 128, 3); else SK(128, 128, 2);
+      } else if (tsel == 2) {
+        if (ns == 4) SK(64, 128, 4); else if (ns == 3) SK(64, 128, 3); else SK(64, 128, 2);
+      } else {
+        if (ns == 4) SK(64, 64, 4); else if (ns == 3) SK(64, 64, 3); else SK(64, 64, 2);
+      }
+#undef SK
+      break;
     }
-    if ((tsel & 128) && !w_fp8 && (tsel & 15) < 5) return 0;  // stream-K combines in-kernel
-    if (w_fp8 && ((tsel & 15) == 4 || (tsel & 15) >= 5)) tsel = (tsel & ~15) | 1;
-    if ((tsel & 256) && (tsel & 15) != 4) {  // split-K combined in-launch
-      int s2 = split_hint, t2 = tsel;
-      gemm_tiled_plan(M, N, K, &t2, &s2, false);
-      int bm, bn;
-      tile_dims(t2 & 15, &bm, &bn);
-      if (s2 > 1 && (int64_t)tiles_of(M, N, bm, bn) * s2 * bm * bn * 4 <= ws_bytes) return 0;
-    }
-    s = split_hint;
-    gemm_tiled_plan(M, N, K, &tsel, &s, false);
-    if ((tsel & 15) == 4 || (tsel & 128)) return 0;
+    case GemmFamily::kWide8:  // 8-wave tiles (bf16 weights)
+#define LT8(BM_, BN_, NS_)                                                                                       \
+  pick(wnt, [&](auto WNT) {                                                                                      \
+    gemm_tiled_kernel<BM_, BN_, NS_, PICKED(WNT), false, 8><<<grid, 512, 0, st>>>(X, ldx, W, ldw, B, Y, ldy, part, M, \
+                                                                                   N, K, act_k, glu_k, nullptr, cnt, qv); \
+  })
+      if (tsel == 5) {
+        if (ns == 3) LT8(256, 128, 3); else LT8(256, 128, 2);
+      } else {
+        if (ns == 4) LT8(256, 64, 4); else if (ns == 3) LT8(256, 64, 3); else LT8(256, 64, 2);
+      }
+#undef LT8
+      break;
+    case GemmFamily::kTiled:
+#define LT(BM_, BN_, NS_)                                                                                        \
+  pick(f8, [&](auto F8) {                                                                                        \
+    pick(wnt, [&](auto WNT) {                                                                                    \
+      gemm_tiled_kernel<BM_, BN_, NS_, PICKED(WNT), PICKED(F8)><<<grid, 256, 0, st>>>(                           \
+          X, ldx, W, ldw, B, Y, ldy, part, M, N, K, act_k, glu_k, wscale, cnt, qv);                              \
+    });                                                                                                          \
+  })
+      if (ns == 3) {
+        if (tsel == 1) LT(128, 128, 3); else if (tsel == 2) LT(64, 128, 3); else LT(64, 64, 3);
+      } else if (ns == 4) {
+        if (tsel == 2) LT(64, 128, 4); else LT(64, 64, 4);
+      } else if (ns == 6) {
+        LT(64, 64, 6);
+      } else {
+        if (tsel == 1) LT(128, 128, 2); else if (tsel == 2) LT(64, 128, 2); else LT(64, 64, 2);
+      }
+#undef LT
+      break;
+    default:
+      return 0;
   }
-  if ((int64_t)s * M * N * 4 > ws_bytes) s = 1;
-  return s > 1 ? s : 0;
+  HIP_CHECK_LAUNCH();
+  return gemm_finish(e, part, M, N, B, Y, ldy, act, g, st);
+}
+
+// Returns the number of fp32 partial slabs [S, M, N] left in `workspace` (partial_out and a split plan without
+// activation / GLU: the consumer - add_norm, rope_cache - reduces them and adds `bias`), or 0 when Y holds the
+// finished bf16 output. w_packed: the panel-packed copy of w, read by plans with the packed bit.
+int launch_gemm(const void* x, int64_t ldx, const void* w, int64_t ldw, bool w_fp8, const void* w_scale,
+                const void* bias, void* y, int64_t ldy, int M, int N, int K, int act, bool glu, void* workspace,
+                int64_t ws_bytes, int nt_hint, int split_hint, bool partial_out, hipStream_t st,
+                const void* w_packed) {
+  bool tuned = false;
+  if (nt_hint == 0 && split_hint == 0) tuned = gemm_tuned_get(M, N, K, glu, w_fp8 ? 1 : 0, &nt_hint, &split_hint);
+  const GemmExec e = gemm_resolve({M, N, K, w_fp8, glu, act, ws_bytes, y != nullptr, partial_out, w_packed != nullptr,
+                                   nullptr, ldx % 8 == 0 && ldw % 8 == 0, nt_hint, split_hint, tuned});
+  if (e.family == GemmFamily::kStreamPanels) {  // every 128-row panel is a call of its own, finished in place
+    for (int m0 = 0; m0 < M; m0 += 128)
+      launch_gemm((const bf16_t*)x + m0 * ldx, ldx, w, ldw, w_fp8, w_scale, bias, (bf16_t*)y + m0 * ldy, ldy,
+                  std::min(128, M - m0), N, K, act, glu, workspace, ws_bytes, e.nt_hint, split_hint, false, st, nullptr);
+    return 0;
+  }
+  return launch_plan(e, (const bf16_t*)x, ldx, e.packed ? w_packed : w, ldw, w_fp8 ? (const float*)w_scale : nullptr,
+                     (const bf16_t*)bias, (bf16_t*)y, ldy, M, N, K, act, glu ? 1 : 0, workspace, st);
 }
 
 // QKV projection with the RoPE + paged-KV write in its LDS-staged epilogue (common.h QkvEpi, tuned kind 3).
@@ -2042,46 +1618,6 @@ int gemm_partial_slabs(int M, int N, int K, bool w_fp8, bool glu, int act, int n
 // combine (the epilogue needs finished sums). Returns -1 when the shape / plan cannot take the epilogue
 // (stream / big-tile / stream-K plans, neox RoPE on tiles that are not head-aligned, workspace too small) -
 // the caller then runs the plain GEMM and the rope_cache kernel; 0 when launched.
-int launch_gemm_qkv(const void* x, int64_t ldx, const void* w, int64_t ldw, const void* bias, void* y, int64_t ldy,
-                    int M, int N, int K, void* workspace, int64_t ws_bytes, int nt_hint, int split_hint,
-                    const QkvEpi& qe, hipStream_t st, const void* w_packed) {
-  if (M == 0) return 0;
-  if (qe.D <= 0) return -1;
-  if (!y) throw std::runtime_error("gemm_qkv: output buffer required");
-  if (qe.D % 8 || N != (qe.nh + 2 * qe.nkv) * qe.D || N % 8 || ldy % 8) return -1;
-  if (qe.do_rope && (qe.rot % 8 || qe.rot > qe.D || (qe.style == 0 && qe.rot % 16))) return -1;
-  bool tuned = false;
-  if (nt_hint == 0 && split_hint == 0) tuned = gemm_tuned_get(M, N, K, false, 3, &nt_hint, &split_hint);
-  if (!k_ok(K, nt_hint))
-    throw std::runtime_error("gemm_qkv: K must be a multiple of 16 (of 8 on gemm_dec / gemm_mid hints)");
-  w = packed_select(w, w_packed, tuned, false, M, &nt_hint);
-  if (nt_hint & 0xff) return -1;  // streaming kernels have no LDS-staged epilogue
-  if ((nt_hint >> 8) & kDecHint) {  // decode GEMM: unsplit, or split and combined in the launch (finished sums)
-    int bn;
-    if (M > 64 || !gemm_dec_bn((nt_hint >> 8) & 15, &bn)) return -1;
-    if (qe.do_rope && qe.style == 0 && bn % qe.D) return -1;
-    const int s = dec_split(M, N, K, split_hint, ws_bytes);
-    const int tsel = (nt_hint >> 8) | (s > 1 ? 256 : 0);
-    if (s > 1 && !dec_combine_fits(N, tsel, s, ws_bytes)) return -1;
-    launch_tiled((const bf16_t*)x, ldx, w, ldw, (const bf16_t*)bias, (bf16_t*)y, ldy, M, N, K, 0, 0, tsel, s,
-                 workspace, ws_bytes, false, st, nullptr, &qe);
-    return 0;
-  }
-  int tsel = nt_hint >> 8, s = split_hint;
-  gemm_tiled_plan(M, N, K, &tsel, &s, false);
-  if ((tsel & 15) == 4 || (tsel & 128)) return -1;
-  int bm, bn;
-  tile_dims(tsel & 15, &bm, &bn);
-  if (qe.do_rope && qe.style == 0 && bn % qe.D) return -1;  // neox partner columns must share the tile
-  if (s > 1) {
-    if ((int64_t)tiles_of(M, N, bm, bn) * s * bm * bn * 4 > ws_bytes) return -1;
-    tsel |= 256;
-  }
-  launch_tiled((const bf16_t*)x, ldx, w, ldw, (const bf16_t*)bias, (bf16_t*)y, ldy, M, N, K, 0, 0, tsel, s, workspace,
-               ws_bytes, false, st, nullptr, &qe);
-  return 0;
-}
-
 int launch_gemm_qkv_args(const void* x, int64_t ldx, const void* w, int64_t ldw, const void* bias, void* y, int64_t ldy,
                          int M, int N, int K, void* workspace, int64_t ws_bytes, int nt_hint, int split_hint,
                          const void* pos, const void* cos_t, const void* sin_t, void* kc, void* vc, const void* slot,
@@ -2089,29 +1625,65 @@ int launch_gemm_qkv_args(const void* x, int64_t ldx, const void* w, int64_t ldw,
                          const void* w_packed) {
   const QkvEpi qe{(const int64_t*)pos, (const float*)cos_t, (const float*)sin_t, (bf16_t*)kc, (bf16_t*)vc,
                   (const int64_t*)slot, nh, nkv, D, rot, block_size, style, do_rope ? 1 : 0};
-  return launch_gemm_qkv(x, ldx, w, ldw, bias, y, ldy, M, N, K, workspace, ws_bytes, nt_hint, split_hint, qe, st,
-                         w_packed);
+  if (M == 0) return 0;
+  if (qe.D <= 0) return -1;
+  if (!y) throw std::runtime_error("gemm_qkv: output buffer required");
+  if (qe.D % 8 || N != (qe.nh + 2 * qe.nkv) * qe.D || N % 8 || ldy % 8) return -1;
+  if (qe.do_rope && (qe.rot % 8 || qe.rot > qe.D || (qe.style == 0 && qe.rot % 16))) return -1;
+  bool tuned = false;
+  if (nt_hint == 0 && split_hint == 0) tuned = gemm_tuned_get(M, N, K, false, 3, &nt_hint, &split_hint);
+  const QkvFacts qf{qe.D, qe.style == 0, qe.do_rope != 0};
+  const GemmExec e = gemm_resolve({M, N, K, false, false, 0, ws_bytes, true, false, w_packed != nullptr, &qf,
+                                   ldx % 8 == 0 && ldw % 8 == 0, nt_hint, split_hint, tuned});
+  if (e.qkv_cannot) return -1;
+  launch_plan(e, (const bf16_t*)x, ldx, e.packed ? w_packed : w, ldw, nullptr, (const bf16_t*)bias, (bf16_t*)y, ldy, M,
+              N, K, 0, 0, workspace, st, &qe);
+  return 0;
 }
 
-void gemm_plan(int M, int N, int K, bool w_fp8, int* nt, int* splitk) {
-  if (gemm_tuned_get(M, N, K, false, w_fp8 ? 1 : 0, nt, splitk)) {
-    if ((*nt >> 8) & kDecHint) {
-      *splitk = ((*nt >> 8) & 256) ? 1 : dec_split(M, N, K, *splitk, INT64_MAX);
-    } else if ((*nt >> 8) & (128 | 256)) {
-      *splitk = 1;  // stream-K / split-K combine finish their tiles in-kernel: no partial slabs for the consumer
-    } else if (*nt >> 8) {  // tiled hint: the split the kernel will really use
-      int tsel = *nt >> 8;
-      gemm_tiled_plan(M, N, K, &tsel, splitk, false);
-    }
-    return;
+// W8A8: per-token fp8 activations xq [M, K] with scales xs, fp8 weights with per-row scales wsc (gemm_plan.h
+// F8Problem: tile / depth / split, ilv = the gemm_mid tiles' software-pipelined k-loop, >= 3 stages).
+// MX-fp8 activations (gemm_mid tiles only): asc = e8m0 scales [M][K / 32] of xq (xs unused: nullptr), and mxq / mxs =
+// a SwiGLU output written as MX-fp8 instead of bf16 y (e4m3 [M][N / 2] with row stride ldy, scales [M][N / 64]; the
+// output tile must hold whole 32-output blocks, BN % 64 == 0, and finish in the launch: no split).
+// Returns the slabs left under partial_out as launch_gemm does.
+int launch_gemm_f8f8(const void* xq, int64_t ldx, const void* xs, const void* wq, int64_t ldw, const void* wsc,
+                     const void* bias, void* y, int64_t ldy, int M, int N, int K, int act, bool glu, int tile,
+                     int depth, int split, void* workspace, int64_t ws_bytes, hipStream_t st, bool partial_out,
+                     bool ilv, void* mxq, void* mxs, const void* asc) {
+  const GemmExec e = gemm_f8f8_resolve({M, N, K, glu, act, tile, depth, split, ws_bytes, y != nullptr, partial_out,
+                                        xs != nullptr, asc != nullptr, mxq != nullptr, mxs && ldy == N / 2});
+  if (e.family == GemmFamily::kNone) return 0;
+  auto A = (const unsigned char*)xq, Bw = (const unsigned char*)wq;
+  auto XS = (const float*)xs, WSc = (const float*)wsc;
+  auto Bi = (const bf16_t*)bias;
+  auto Y = (bf16_t*)y;
+  const int g = glu ? 1 : 0;
+  if (e.family == GemmFamily::kF8Big) {
+    gemm_big_kernel<true><<<tiles_of(M, N, 256, 256), 512, 0, st>>>(xq, ldx, wq, ldw, Bi, Y, ldy, M, N, K, act, g, XS,
+                                                                    WSc, g_big_group_m);
+    HIP_CHECK_LAUNCH();
+    return 0;
   }
-  if (M <= 16 || (w_fp8 && M > 128)) {
-    gemm_stream_plan(std::min(M, 128), N, K, nt, splitk);
+  float* part = e.split > 1 ? (float*)workspace : nullptr;
+  const int act_k = e.split > 1 ? 0 : act, glu_k = e.split > 1 ? 0 : g;
+  dim3 grid(tiles_of(M, N, e.bm, e.bn), e.split);
+#define LF(BM_, BN_, NS_) \
+  gemm_f8f8_kernel<BM_, BN_, NS_><<<grid, 256, 0, st>>>(A, ldx, XS, Bw, ldw, WSc, Bi, Y, ldy, part, M, N, K, act_k, glu_k)
+  if (e.family == GemmFamily::kMid) {
+    QkvEpi mx{};
+    mx.mxq = (unsigned char*)mxq;
+    mx.mxs = (unsigned char*)mxs;
+    launch_gemm_mid(e.tile, e.depth, e.wnt, (const bf16_t*)xq, ldx, (const bf16_t*)wq, ldw, Bi, Y, ldy, part, M, N, K,
+                    act_k, glu_k, e.split, st, nullptr, mxq ? &mx : nullptr, XS, WSc, ilv, (const unsigned char*)asc);
+  } else if (e.tile == 1) {
+    if (e.depth >= 3) LF(128, 128, 3); else LF(128, 128, 2);
+  } else if (e.tile == 2) {
+    if (e.depth >= 4) LF(64, 128, 4); else if (e.depth == 3) LF(64, 128, 3); else LF(64, 128, 2);
   } else {
-    int tsel = 0, s = 0;
-    gemm_tiled_plan(M, N, K, &tsel, &s, false);
-    *nt = tsel << 8;
-    *splitk = s;
+    if (e.depth >= 4) LF(64, 64, 4); else if (e.depth == 3) LF(64, 64, 3); else LF(64, 64, 2);
   }
+#undef LF
+  HIP_CHECK_LAUNCH();
+  return gemm_finish(e, part, M, N, Bi, Y, ldy, act, g, st);
 }
-

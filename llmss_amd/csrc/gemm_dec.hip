@@ -29,6 +29,7 @@
 // 2048, range = the packed bytes from the tile's first panel; the LDS image and everything after it are the same, so
 // a packed plan's output is bit-identical to its row-major sibling's.
 #include "common.h"
+#include "gemm_plan.h"
 
 namespace {
 
@@ -288,14 +289,6 @@ static void dec_launch(dim3 grid, hipStream_t st, const bf16_t* X, int64_t ldx, 
   }
 }
 
-// BN code (hint tile bits): 1 = 16, 2 = 32, 3 = 48, 4 = 64, 5 = 96 columns per workgroup
-bool gemm_dec_bn(int code, int* bn) {
-  static constexpr int kBN[6] = {0, 16, 32, 48, 64, 96};
-  if (code < 1 || code > 5) return false;
-  *bn = kBN[code];
-  return true;
-}
-
 // ring depth actually used: the deepest <= want (2..4) whose rings fit the 160 KiB LDS
 static int dec_depth(int mt, int bn, int want) {
   int ns = std::max(2, std::min(want, 4));
@@ -310,8 +303,9 @@ static int dec_depth(int mt, int bn, int want) {
 void launch_gemm_dec(int code, int depth, const bf16_t* X, int64_t ldx, const bf16_t* W, int64_t ldw,
                      const bf16_t* bias, bf16_t* Y, int64_t ldy, float* part, int M, int N, int K, int act, int glu,
                      int split, hipStream_t st, const QkvEpi* qe, int* cnt, bool packed = false) {
-  int bn;
-  if (!gemm_dec_bn(code, &bn)) throw std::runtime_error("gemm_dec: bad tile code");
+  const GemmTile* tile = gemm_tile(code, true);  // BN code -> columns per workgroup (gemm_plan.h kGemmTiles)
+  if (!tile) throw std::runtime_error("gemm_dec: bad tile code");
+  const int bn = tile->bn;
   if (M < 1 || M > 64) throw std::runtime_error("gemm_dec: M must be 1..64");
   if (glu && (bn % 32)) throw std::runtime_error("gemm_dec: SwiGLU needs 32-column tile pairs");
   if ((uint64_t)64 * ldx * 2 >= (1ull << 31) || (!packed && (uint64_t)bn * ldw * 2 >= (1ull << 31)) ||

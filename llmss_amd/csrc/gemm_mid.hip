@@ -17,6 +17,7 @@
 // Tiles are larger per wave (32-64 MFMAs per k-step) so the fixed per-step cost (barrier, counted
 // vmcnt wait, staging issue) is amortised. Ring of NS stages, stage t+NS-1 issued while t computes.
 #include "common.h"
+#include "gemm_plan.h"
 
 // The buffer descriptor is built and used only inside the kernel body, and every offset argument of
 // the buffer builtins is cast to uint32_t explicitly: otherwise the host compilation pass of this
@@ -467,30 +468,11 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_mid_kernel(const bf16_t* __
                                                         act, glu, qe);
 }
 
-// tsel 8: 128x128 (2x2 waves), 9: 256x128 (4x2), 10: 64x256 (1x4), 11: 64x128 (1x4), 12: 128x256 (2x4),
-// 13: 64x192 (2x2; a 12288-column QKV is 64 tiles, 4096 columns 22: one workgroup per CU without a K split),
-// 14: 64x32 (4x1; narrow projections without a K split: GPT-2-XL's 6400-column MLP up is 200 workgroups),
-// 15: 64x96 (4x1; Llama-2-7B's 22016-column gate/up is 230 workgroups: one wave of the chip, no K split),
-// 7: 64x48 (2x1 waves: 48 rows do not split over 4 waves in 8-row staging pieces; a 12288-column QKV is
-//    exactly 256 workgroups without a K split)
+// tile code -> dims and wave grid: the gemm_mid rows of the tile table (gemm_plan.h kGemmTiles)
 static bool mid_layout(int tsel, int* bm, int* bn, int* wm, int* wn) {
-  switch (tsel) {
-    case 8: *bm = 128; *bn = 128; *wm = 2; *wn = 2; return true;
-    case 9: *bm = 256; *bn = 128; *wm = 4; *wn = 2; return true;
-    case 10: *bm = 64; *bn = 256; *wm = 1; *wn = 4; return true;
-    case 11: *bm = 64; *bn = 128; *wm = 1; *wn = 4; return true;
-    case 12: *bm = 128; *bn = 256; *wm = 2; *wn = 4; return true;
-    case 13: *bm = 64; *bn = 192; *wm = 2; *wn = 2; return true;
-    case 14: *bm = 64; *bn = 32; *wm = 4; *wn = 1; return true;
-    case 15: *bm = 64; *bn = 96; *wm = 4; *wn = 1; return true;
-    case 7: *bm = 64; *bn = 48; *wm = 2; *wn = 1; return true;
-    default: return false;
-  }
-}
-bool gemm_mid_dims(int tsel, int* bm, int* bn, int* threads) {
-  int wm, wn;
-  if (!mid_layout(tsel, bm, bn, &wm, &wn)) return false;
-  *threads = 64 * wm * wn;
+  const GemmTile* t = gemm_tile(tsel);
+  if (!t || t->family != GemmFamily::kMid) return false;
+  *bm = t->bm; *bn = t->bn; *wm = t->wm; *wn = t->wn;
   return true;
 }
 

@@ -259,12 +259,12 @@ class LLMEngine:
 
     def _pack_decode_weights(self) -> int:
         """Panel-packed twins (ops.hip.pack_panels) of the projections whose plan at some decode row count reads
-        packed weights (hint bit 2048 in the native plan table: the autotuner's choice, or gemm_tuned_set). Made after
+        packed weights (plans.PACKED in the native plan table: the autotuner's choice, or gemm_tuned_set). Made after
         tuning and before graph capture, kept on the model's Linear objects for the model's lifetime - the captured
         graphs hold their addresses. Prefill and every M > 64 call keep reading the row-major weight. The KV cache is
         already sized, so ``num_blocks`` does not change; a projection whose twin would not leave 2 GiB free is skipped
         (its packed plans then run their row-major siblings: the same kernels, the same bits). Returns the bytes added."""
-        from ..ops.autotune import PACKED
+        from ..ops.plans import PACKED, describe
 
         lib = _hip_ops.lib()
         ms = [m for m in self.decode_batch_sizes() if m <= 64]
@@ -284,8 +284,8 @@ class LLMEngine:
                         plans[(m, kind)] = t
             top = max(ms) if ms else 0
             won = self.tuned.get(("qkv_epi" if (top, 3) in plans else name, top)) or self.tuned.get((name, top))
-            won_s = f"; tuner at M={top}: hint {won[0]:#x} split {won[1]} {won[2]:.1f} us (default {won[3]:.1f})" \
-                if won else ""
+            won_s = (f"; tuner at M={top}: hint {won[0]:#x} split {won[1]} ({describe(won[0], won[1])}) "
+                     f"{won[2]:.1f} us (default {won[3]:.1f})") if won else ""
             if not plans:
                 log.info("packed weights: %s [%d, %d] stays row-major in every decode bucket%s", name, lin.N, lin.K,
                          won_s)
@@ -301,8 +301,9 @@ class LLMEngine:
                     l.w_packed = _hip_ops.pack_panels(l.w)
             total += need
             log.info("packed weights: %s [%d, %d] x %d packed, +%.3f GB; plans %s%s", name, lin.N, lin.K, len(lins),
-                     need / 1e9, ", ".join(f"M={m}{'/qkv-epilogue' if k == 3 else ''}: hint {t[0]:#x} split {t[1]}"
-                                          for (m, k), t in sorted(plans.items())), won_s)
+                     need / 1e9,
+                     ", ".join(f"M={m}{'/qkv-epilogue' if k == 3 else ''}: hint {t[0]:#x} split {t[1]} ({describe(*t)})"
+                               for (m, k), t in sorted(plans.items())), won_s)
         if total:
             torch.cuda.synchronize(self.device)
         return total

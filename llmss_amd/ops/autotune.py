@@ -1,6 +1,6 @@
 """GEMM autotuner for the shapes an engine runs (decode batch buckets x layer projections).
 
-The static planner in ``csrc/gemm.hip`` is a good default, but the best (kernel, tile, LDS ring
+The static planner in ``csrc/gemm_plan.h`` is a good default, but the best (kernel, tile, LDS ring
 depth, split-K) choice for a memory-bound decode GEMM moves with M, N and K by 10-40% in ways a
 rule does not capture (``bench/gemm_bench.py --sweep``). At engine start every decode shape is
 timed over a candidate list and the winner goes into the native plan table, which every later
@@ -23,25 +23,14 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 
 from ..utils.logging import get_logger
+from . import plans as P
+from .plans import PACKED, packed_twin  # noqa: F401  (re-exported: tests and the engine import them from here)
 
 log = get_logger(__name__)
 
 _SLAB_READ_BPS = 4.0e12  # consumer-side fp32 partial reads (add_norm / rope), bytes/s
 ILV_MIN_M = 128  # smallest M whose plans include the interleaved ring (profiles/r4_gemm/sweep512_ilv.log)
 FINALISTS = 6  # candidates re-timed at full length after the short first round
-PACKED = 2048 << 8  # nt_hint bit 19: the plan reads the panel-packed copy of the weight (ops.hip.PACKED_HINT)
-_PACKED_MID = (7, 10, 11, 13, 14, 15)  # the 64-row gemm_mid tiles: the ones with a packed-weight variant
-
-
-def packed_twin(M: int, nt: int, fp8: bool = False) -> Optional[int]:
-    """The hint of the same plan reading panel-packed weights, or None where the kernel has no such variant:
-    gemm_dec and the 64-row gemm_mid tiles (plain, in-launch combine), bf16 weights, M <= 64."""
-    t = nt >> 8
-    if fp8 or M > 64 or nt & 0xff or nt >> 20 or t & (128 | 512 | 64):
-        return None
-    if t & 1024 or (t & 15) in _PACKED_MID:
-        return nt | PACKED
-    return None
 
 
 @dataclass(frozen=True)
@@ -55,46 +44,42 @@ class GemmShape:
 
 
 def candidates(M: int, N: int, K: int, glu: bool, fp8: bool) -> List[Tuple[int, int]]:
-    """(nt_hint, split) pairs; nt_hint encodings are documented in csrc/gemm.hip launch_gemm."""
+    """(nt_hint, split) pairs; the nt_hint encoding is named in ops/plans.py (csrc/gemm_plan.h documents it)."""
     out: List[Tuple[int, int]] = []
     splits = (1, 2, 4, 8)
     if fp8 or M <= 64:  # weight-streaming kernels (nt + 16 * variant); at M = 33-64 four 16-row MFMA tiles per wave
-        out += [(nt + 16 * v, s) for v, nt, s in itertools.product((1, 2), (1, 2), splits)]
+        out += [(P.stream_hint(nt, v), s) for v, nt, s in itertools.product((1, 2), (1, 2), splits)]
     if fp8:  # tiled kernel with fp8 weight tiles (no stream-K / big-tile variants)
         if M > 16:
-            out += [((t | d) << 8, s) for t, d in ((3, 16), (3, 32), (2, 16), (2, 32)) for s in splits]
-        if M >= 32:  # W8A8: per-token fp8 activations on the MX-fp8 matrix cores (ops/hip.py W8A8_FLAG)
-            from .hip import W8A8_FLAG
-
+            out += [(P.tile_hint(t, d), s) for t, d in ((3, 16), (3, 32), (2, 16), (2, 32)) for s in splits]
+        if M >= 32:  # W8A8: per-token fp8 activations on the MX-fp8 matrix cores (plans.W8A8)
             tiles = [3, 2] + ([1] if M > 64 else [])
-            out += [(W8A8_FLAG | (t << 8) | (d << 12), s) for t in tiles for d in (2, 3, 4) for s in splits
+            out += [(P.w8a8_hint(t, d), s) for t in tiles for d in (2, 3, 4) for s in splits
                     if not (t == 1 and d > 3)]
             if K % 128 == 0:  # gemm_mid tiles with the fp8 MFMA (buffer-descriptor staging, csrc/gemm_mid.hip)
                 mt = [11, 10, 13, 15, 7] + ([8, 12] if M > 64 else []) + ([9] if M >= 256 else [])
-                out += [(W8A8_FLAG | (t << 8) | (d << 12), s) for t in mt for d in (3, 4)
+                out += [(P.w8a8_hint(t, d), s) for t in mt for d in (3, 4)
                         for s in (1, 2, 3, 4, 5, 6, 8)]
-                if M >= ILV_MIN_M:  # their software-pipelined k-loop (W8A8_ILV), 3-5 stages, 4-wave tiles
-                    from .hip import W8A8_ILV
-
-                    out += [(W8A8_FLAG | W8A8_ILV | (t << 8) | (d << 12), s) for t in mt if t not in (9, 12)
+                if M >= ILV_MIN_M:  # their software-pipelined k-loop (plans.ILV), 3-5 stages, 4-wave tiles
+                    out += [(P.w8a8_hint(t, d, P.ILV), s) for t in mt if t not in (9, 12)
                             for d in (3, 4, 5) for s in (1, 2, 4) if (K // 128) // s >= 3]
             if M >= 256 and K % 128 == 0:
-                out.append((W8A8_FLAG | (4 << 8), 1))
+                out.append((P.w8a8_hint(4), 1))
         return out
-    # tiled: tile << 8 | depth code << 12   (tile 1: 128x128, 2: 64x128, 3: 64x64; depth 2/3/4/6)
+    # tiled: (tile, depth field)   (tile 1: 128x128, 2: 64x128, 3: 64x64; depth field 0 / 16 / 32 / 48 = 2/3/4/6 stages)
     tiles = [(3, (0, 16, 32, 48)), (2, (0, 16, 32))]
     if M > 32:
         tiles.append((1, (0, 16)))
     for t, depths in tiles:
         for d in depths:
-            out += [((t | d) << 8, s) for s in splits]
-    if M > 32:  # stream-K (tile | depth | 128) << 8, split = workgroups per CU
+            out += [(P.tile_hint(t, d), s) for s in splits]
+    if M > 32:  # stream-K, split = workgroups per CU
         for t, d in ((1, 0), (1, 16), (2, 16), (2, 32), (3, 16), (3, 32)):
-            out += [((t | d | 128) << 8, g) for g in (1, 2, 3)]
+            out += [(P.tile_hint(t, d, P.STREAM_K), g) for g in (1, 2, 3)]
     if M >= 256 and K % 64 == 0:
-        out.append((4 << 8, 1))
+        out.append((P.tile_hint(4), 1))
     if M >= 128:  # 8-wave 256x128 (5) / 256x64 (6) tiles: one workgroup per CU, deep split-K
-        out += [((t | d) << 8, s) for t, d in ((5, 16), (6, 16), (6, 32)) for s in (2, 4, 8, 12, 16)]
+        out += [(P.tile_hint(t, d), s) for t, d in ((5, 16), (6, 16), (6, 32)) for s in (2, 4, 8, 12, 16)]
     # gemm_mid (buffer-descriptor staging, csrc/gemm_mid.hip): 8 = 128x128, 9 = 256x128, 10 = 64x256,
     # 11 = 64x128, 12 = 128x256; depth code 16 / 32 = 3 / 4 stages (clamped to the LDS)
     mids = [(10, 16), (11, 16), (11, 32), (13, 16), (13, 32), (14, 32), (14, 48), (15, 16), (15, 32), (7, 32), (7, 48)]
@@ -105,18 +90,19 @@ def candidates(M: int, N: int, K: int, glu: bool, fp8: bool) -> List[Tuple[int, 
     # odd splits too: with one workgroup per CU the best grid lands just under a multiple of the 256 CUs
     # (64 x 256 tiles of a 12288-column QKV: 48 tiles x 5 = 240 workgroups)
     nk = -(-K // 64)
-    out += [((t | d) << 8, s) for t, d in mids for s in (1, 2, 3, 4, 5, 6, 8, 11, 12) if s == 1 or nk // s >= 2]
-    # K split over the waves of a workgroup, wave-private rings (hint bit 1024, csrc/gemm_dec.hip): M <= 64, column
+    out += [(P.tile_hint(t, d), s) for t, d in mids for s in (1, 2, 3, 4, 5, 6, 8, 11, 12) if s == 1 or nk // s >= 2]
+    # K split over the waves of a workgroup, wave-private rings (plans.DEC, csrc/gemm_dec.hip): M <= 64, column
     # widths 16-64, grids of 64-1024 workgroups (profiles/r6_dec: GPT-2-XL's up projection 9.9 vs 11.2 us)
     if M <= 64:
-        for code, bn in ((1, 16), (2, 32), (3, 48), (4, 64)):
-            tiles = -(-N // bn)
-            out += [((code | 32 | 1024) << 8, s) for s in (1, 2, 3, 4, 5, 8, 10) if s <= nk and 64 <= tiles * s <= 1024]
+        for code in (1, 2, 3, 4):
+            tiles = -(-N // P.tile(code, dec=True).bn)
+            out += [(P.tile_hint(code, P.D4, P.DEC), s) for s in (1, 2, 3, 4, 5, 8, 10)
+                    if s <= nk and 64 <= tiles * s <= 1024]
             # (its in-launch split-K combine, hint bit 256, is selectable but not a candidate: 15.2 us at best for
             # GPT-2-XL's up projection against 10.6 unsplit, profiles/r6_dec)
     # interleaved ring (hint bit 512, csrc/gemm_mid.hip ILV): >= 3 stages
     if M >= ILV_MIN_M and K % 64 == 0:
-        out += [((t | d | 512) << 8, s) for t, d in mids if d >= 16 for s in (1, 2, 3, 4, 5, 6, 8)
+        out += [(P.tile_hint(t, d, P.ILV), s) for t, d in mids if d >= 16 for s in (1, 2, 3, 4, 5, 6, 8)
                 if s == 1 or nk // s >= 3]
     # split-K combined inside the launch (hint bit 256, csrc/common.h splitk_combine): finished bf16
     # output with no reduce launch - for SwiGLU / activation GEMMs and row-parallel outputs that an
@@ -127,8 +113,8 @@ def candidates(M: int, N: int, K: int, glu: bool, fp8: bool) -> List[Tuple[int, 
     if M >= 256:
         comb += [(9, 0)]
     nk = -(-K // 64)
-    out += [((t | d | 256) << 8, s) for t, d in comb for s in (2, 3, 4, 6, 8) if nk // s >= 2]
-    # every gemm_dec / 64-row gemm_mid candidate once more on panel-packed weights (hint bit 2048): the same kernel
+    out += [(P.tile_hint(t, d, P.COMBINE), s) for t, d in comb for s in (2, 3, 4, 6, 8) if nk // s >= 2]
+    # every gemm_dec / 64-row gemm_mid candidate once more on panel-packed weights (plans.PACKED): the same kernel
     # and the same output bits, the weight stream in contiguous 2-KiB blocks (profiles/packed_decode)
     out += [(packed_twin(M, nt), s) for nt, s in out if packed_twin(M, nt)]
     return out
@@ -208,7 +194,7 @@ def tune_shape(M: int, shape: GemmShape, device, weight_budget: int = 600 << 20,
     # two rounds (engine start-up time): every candidate on a short graph (4 calls), then the
     # FINALISTS fastest of them again at the full `iters` - a short graph ranks plans that differ by > ~3 % the
     # same way, and the final choice is made on the long timings only
-    # Packed twins (hint bit 2048) take no part in the choice of the plan: which kernel, tile, depth and split runs
+    # Packed twins (plans.PACKED) take no part in the choice of the plan: which kernel, tile, depth and split runs
     # fixes the summation order and so the output bits, and that choice stays what it is without packed weights. Only
     # then is the winner's twin - the same kernel, the same bits - timed exactly like it and taken if it is faster.
     quick = []
@@ -260,21 +246,23 @@ def model_shapes(model) -> Dict[str, GemmShape]:
 def qkv_epi_candidates(M: int, N: int, K: int, D: int, neox_rope: bool) -> List[Tuple[int, int]]:
     """(nt_hint, split) plans that can run the QKV RoPE + KV-write epilogue: tiled / gemm_mid tiles, unsplit
     or combined in-launch (a split plan runs as a combine); neox RoPE needs head-aligned tiles (BN % D)."""
-    tiles = [(3, 64, (16, 32)), (2, 128, (16, 32)), (11, 128, (16, 32)), (10, 256, (16,)), (13, 192, (16, 32)), (14, 32, (32, 48)), (15, 96, (16, 32)), (7, 48, (32, 48))]
+    tiles = [(3, (16, 32)), (2, (16, 32)), (11, (16, 32)), (10, (16,)), (13, (16, 32)), (14, (32, 48)), (15, (16, 32)),
+             (7, (32, 48))]
     if M > 64:
-        tiles += [(1, 128, (0, 16)), (8, 128, (16,)), (12, 256, (16,))]
+        tiles += [(1, (0, 16)), (8, (16,)), (12, (16,))]
     if M >= 256:
-        tiles += [(9, 128, (0,))]
+        tiles += [(9, (0,))]
     nk = -(-K // 64)
     out = []
     if M <= 64:  # the K-split-wave decode kernel (csrc/gemm_dec.hip), unsplit (its in-launch combine measured slower)
-        out += [((code | 32 | 1024) << 8, 1) for code, bn in ((1, 16), (2, 32), (3, 48), (4, 64))
-                if not (neox_rope and bn % D)]
-    for t, bn, depths in tiles:
-        if neox_rope and bn % D:
+        out += [(P.tile_hint(code, P.D4, P.DEC), 1) for code in (1, 2, 3, 4)
+                if not (neox_rope and P.tile(code, dec=True).bn % D)]
+    for t, depths in tiles:
+        if neox_rope and P.tile(t).bn % D:
             continue
         for d in depths:
-            out += [((t | d | (256 if s > 1 else 0)) << 8, s) for s in (1, 2, 3, 4, 6, 8) if s == 1 or nk // s >= 2]
+            out += [(P.tile_hint(t, d, P.COMBINE if s > 1 else 0), s) for s in (1, 2, 3, 4, 6, 8)
+                    if s == 1 or nk // s >= 2]
     out += [(packed_twin(M, nt), s) for nt, s in out if packed_twin(M, nt)]  # the same plans on packed weights
     return out
 
@@ -413,6 +401,8 @@ def tune_model(model, ms: Sequence[int], native=None) -> Dict[Tuple[str, int], T
             if key not in done:
                 done[key] = tune_shape(rep[M], shp, dev)
             nt, s, t, t0_us = done[key]
+            log.debug("tuned %s M=%d: %#x split %d (%s) %.1f us (static %.1f)", name, M, nt, s, P.describe(nt, s), t,
+                      t0_us)
             if nt:
                 lib.gemm_tuned_set(M, shp.N, shp.K, shp.glu, int(shp.fp8), nt, s)
             res[(name, M)] = done[key]

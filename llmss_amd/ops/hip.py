@@ -15,6 +15,7 @@ from typing import Optional
 
 import torch
 
+from . import plans
 from . import reference as _ref
 
 _C = None
@@ -431,11 +432,8 @@ class PartialSum:
 
 _FP8_PREFILL_M = 128  # untuned fp8 calls above this M run W8A8 (compute-bound); below, W8A16 weight streaming
 
-# nt_hint flag of a W8A8 plan (the tuned table's fp8 entries or an explicit hint): tile = (nt >> 8) & 15
-# (1 128x128, 2 64x128, 3 64x64, 4 256x256, 7-15 the gemm_mid tiles), ring depth = (nt >> 12) & 15, split-K = the
-# plan's split; W8A8_ILV: the gemm_mid tiles' software-pipelined k-loop (the bf16 plans' interleave bit 512 << 8)
-W8A8_FLAG = 1 << 20
-W8A8_ILV = 512 << 8
+# the hint fields are named in ops/plans.py; these are its names as tests and callers import them from here
+W8A8_FLAG, W8A8_ILV, PACKED_HINT, MID_TILE_BN = plans.W8A8, plans.ILV, plans.PACKED, plans.MID_TILE_BN
 
 
 class _QuantScratch:
@@ -500,15 +498,18 @@ class _MxScratch:
 
 
 _MXSCRATCH = _Slotted(_MxScratch)
-MID_TILE_BN = {7: 48, 8: 128, 9: 128, 10: 256, 11: 128, 12: 256, 13: 192, 14: 32, 15: 96}  # gemm_mid tile -> BN
+
+
+def _w8a8_mid(nt) -> bool:
+    """``nt`` is a W8A8 plan on a gemm_mid tile (the MX-capable kernels)."""
+    h = plans.decode(nt)
+    return h.w8a8 and h.tile in MID_TILE_BN
 
 
 def _w8a8_mid_plan(M, N, K, glu):
     """The tuned W8A8 plan of this shape when it runs a gemm_mid tile (the MX-capable kernels), else None."""
     tuned = lib().gemm_tuned_get(M, N, K, bool(glu), 1)
-    if tuned is None or not tuned[0] & W8A8_FLAG or ((tuned[0] >> 8) & 15) not in MID_TILE_BN:
-        return None
-    return tuned
+    return tuned if tuned is not None and _w8a8_mid(tuned[0]) else None
 
 
 def mx_mlp_ok(M: int, up, down) -> bool:
@@ -518,7 +519,7 @@ def mx_mlp_ok(M: int, up, down) -> bool:
     if up.w_scale is None or down.w_scale is None or not up.glu or up.N % 128 or down.K % 128 or up.N // 2 != down.K:
         return False
     pu, pd = _w8a8_mid_plan(M, up.N, up.K, True), _w8a8_mid_plan(M, down.N, down.K, False)
-    return bool(pu and pd and pu[1] == 1 and MID_TILE_BN[(pu[0] >> 8) & 15] % 64 == 0)
+    return bool(pu and pd and pu[1] == 1 and MID_TILE_BN[plans.decode(pu[0]).tile] % 64 == 0)
 
 
 def linear_w8a8(x, wq, w_scale, bias=None, act="none", glu=False, out=None, tile=0, depth=0, split=0,
@@ -622,9 +623,6 @@ def dequant_fp8_rows(q, scale, out=None):
     return w
 
 
-PACKED_HINT = 2048 << 8  # nt_hint bit 19: the plan streams the panel-packed copy of the weight (csrc/gemm.hip)
-
-
 def pack_panels(w, out=None):
     """Panel-packed copy ``[ceil(N/16)][ceil(K/64)][16][64]`` of a row-major bf16 ``[N, K]`` weight of any row stride,
     zeros past N and K (csrc/pack.hip; bit-equal to ``reference.pack_panels``): what a plan with :data:`PACKED_HINT`
@@ -660,11 +658,10 @@ def linear(x, w, bias=None, act="none", glu=False, w_scale=None, out=None, nt_hi
     if isinstance(x, MxAct) or mx_out:
         _check(w_scale is not None, "MX-fp8 activations need fp8 weights")
         plan = (nt_hint, split_hint) if nt_hint else _w8a8_mid_plan(M, w.shape[0], K, glu)
-        _check(plan is not None and plan[0] & W8A8_FLAG and ((plan[0] >> 8) & 15) in MID_TILE_BN,
-               "MX-fp8 activations need a W8A8 gemm_mid plan")
-        nt, sp = plan
-        return linear_w8a8(x, w, w_scale, bias, act, glu, out, (nt >> 8) & 15, (nt >> 12) & 15, sp,
-                           partial_ok=partial_ok, ilv=bool(nt & W8A8_ILV), mx_out=mx_out)
+        _check(plan is not None and _w8a8_mid(plan[0]), "MX-fp8 activations need a W8A8 gemm_mid plan")
+        h = plans.decode(plan[0])
+        return linear_w8a8(x, w, w_scale, bias, act, glu, out, h.tile, h.depth, plan[1], partial_ok=partial_ok,
+                           ilv=h.ilv, mx_out=mx_out)
     _bf16_rows(x, "x")
     fp8 = w_scale is not None
     if fp8:
@@ -674,8 +671,9 @@ def linear(x, w, bias=None, act="none", glu=False, w_scale=None, out=None, nt_hi
         if tuned is not None and tuned[0] & W8A8_FLAG:  # the autotuner picked W8A8 for this M
             nt_hint, split_hint = tuned
         if nt_hint & W8A8_FLAG:
-            return linear_w8a8(x, w, w_scale, bias, act, glu, out, (nt_hint >> 8) & 15, (nt_hint >> 12) & 15,
-                               split_hint, partial_ok=partial_ok, ilv=bool(nt_hint & W8A8_ILV))
+            h = plans.decode(nt_hint)
+            return linear_w8a8(x, w, w_scale, bias, act, glu, out, h.tile, h.depth, split_hint, partial_ok=partial_ok,
+                               ilv=h.ilv)
         if M > _FP8_PREFILL_M and not nt_hint and tuned is None:  # compute-bound: per-token fp8 activations
             return linear_w8a8(x, w, w_scale, bias, act, glu, out, partial_ok=partial_ok)  # on the MX-fp8 MFMA
     else:

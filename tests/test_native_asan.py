@@ -31,6 +31,21 @@ def test_runtime_under_asan_ubsan(tmp_path):
     assert "ALL OK" in r.stdout
 
 
+@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
+def test_gemm_plan_under_asan_ubsan(tmp_path):
+    """The GEMM plan resolver (csrc/gemm_plan.h) under ASan + UBSan over the whole hint field space and fixed-seed
+    random 32-bit hints: every call throws std::runtime_error or returns a launchable plan
+    (tests/native/gemm_plan_host_test.cpp)."""
+    exe = str(tmp_path / "gemm_plan_host_test")
+    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined",
+           "-fno-sanitize-recover=undefined", os.path.join(HERE, "native", "gemm_plan_host_test.cpp"), "-o", exe,
+           "-pthread"]
+    subprocess.run(cmd, check=True, capture_output=True, timeout=300)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:verify_asan_link_order=0", UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120, env=env)
+    assert r.returncode == 0 and "ALL OK" in r.stdout, r.stdout + r.stderr
+
+
 CTRL_MODES = ("threads", "timeout", "procs", "dead")
 
 
