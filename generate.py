@@ -42,6 +42,12 @@ def get_args(argv=None):
     parser.add_argument("--logprobs", type=int, default=None,
                         help="print, per generated token, its log-probability under the raw model distribution and the "
                              "N most likely tokens (0..20; 0: the token's alone)")
+    parser.add_argument("--repetition_penalty", type=float, default=1.0,
+                        help="> 0: the logit x of a token seen in the prompt or the output becomes x / r (x > 0) or x * r")
+    parser.add_argument("--presence_penalty", type=float, default=0.0,
+                        help="[-2, 2]: subtracted from the logit of every token generated so far")
+    parser.add_argument("--frequency_penalty", type=float, default=0.0,
+                        help="[-2, 2]: subtracted once per occurrence among the generated tokens")
     return parser.parse_args(argv)
 
 
@@ -58,6 +64,20 @@ def recompute_generate(model, prompts, params, eos, lp_out=None):
     done = [False] * len(prompts)
     nokv = [(None, None)] * model.cfg.num_layers
     maxlen = model.cfg.max_position_embeddings
+    V = model.cfg.vocab_size
+    state = None
+    if params.has_penalties and model.dtype not in (torch.bfloat16, torch.float32):
+        raise ValueError(f"penalties need bfloat16 or float32 logits (--dtype bf16 | fp32), the model computes "
+                         f"{model.dtype}")
+    if params.has_penalties:  # one state row per prompt: its tokens flagged now, every generated token counted below
+        state = torch.zeros(len(prompts), V, dtype=torch.int32, device=dev)
+        words = [ops.penalty_words(p, []) for p in prompts]
+        cu = [0]
+        for t, _ in words:
+            cu.append(cu[-1] + t.size)
+        ops.penalty_reset(state, torch.arange(len(prompts), dtype=torch.int32, device=dev),
+                          torch.tensor(cu, dtype=torch.int32, device=dev),
+                          *(torch.cat([torch.from_numpy(w[k]) for w in words]).to(dev) for k in (0, 1)))
     for step in range(params.max_new_tokens):
         live = [i for i in range(len(seqs)) if not done[i]]
         if not live:
@@ -75,7 +95,14 @@ def recompute_generate(model, prompts, params, eos, lp_out=None):
         topk = torch.full((n,), params.k_top_k, dtype=torch.int32, device=dev)
         topp = torch.full((n,), params.k_top_p, dtype=torch.float32, device=dev)
         seeds = torch.tensor([step_seed(params.resolved_seed() + i, step) for i in live], dtype=torch.int64, device=dev)
-        tok = ops.sample(logits, temp, topk, topp, seeds, vocab=model.cfg.vocab_size)
+        plogits = logits
+        if state is not None:  # register each sequence's previous token, then penalise (log-probabilities stay raw)
+            pen = (torch.full((n,), v, dtype=torch.float32, device=dev) for v in
+                   (params.repetition_penalty, params.presence_penalty, params.frequency_penalty))
+            plogits = ops.apply_penalties(logits, state, torch.tensor(live, dtype=torch.int32, device=dev),
+                                          torch.tensor([outs[i][-1] if outs[i] else -1 for i in live], device=dev),
+                                          *pen, 0, V)
+        tok = ops.sample(plogits, temp, topk, topp, seeds, vocab=model.cfg.vocab_size)
         if lp_out is not None:
             nlp = params.logprobs
             lp, top, tids = (x.cpu().tolist() for x in ops.token_logprobs(logits, model.cfg.vocab_size, tok, nlp))
@@ -97,6 +124,9 @@ def main(argv=None):
     assert 0.0 < args.top_p <= 1.0, "Value of top_p is not valid."
     assert args.top_k >= 0, "Value of top_k is not valid."
     assert args.logprobs is None or 0 <= args.logprobs <= 20, "Value of logprobs is not valid."
+    assert 0.0 < args.repetition_penalty < float("inf"), "Value of repetition_penalty is not valid."
+    assert -2.0 <= args.presence_penalty <= 2.0, "Value of presence_penalty is not valid."
+    assert -2.0 <= args.frequency_penalty <= 2.0, "Value of frequency_penalty is not valid."
 
     from llmss_amd.engine import LLMEngine, SamplingParams, build_model
     from llmss_amd.parallel.dist import initialize_distributed
@@ -119,7 +149,8 @@ def main(argv=None):
         seed = tp.broadcast_object(int.from_bytes(os.urandom(4), "little") if rank == 0 else None)
     params = SamplingParams(max_new_tokens=args.max_new_tokens, is_greedy=args.is_greedy,
                             temperature=args.temperature, top_p=args.top_p, top_k=args.top_k, seed=seed,
-                            logprobs=args.logprobs)
+                            logprobs=args.logprobs, repetition_penalty=args.repetition_penalty,
+                            presence_penalty=args.presence_penalty, frequency_penalty=args.frequency_penalty)
     eos = getattr(tokenizer, "eos_token_id", None)
     prompts = [encode(tokenizer, p) for p in args.prompts]
     max_len = model.cfg.max_position_embeddings
@@ -129,7 +160,8 @@ def main(argv=None):
     if args.use_cache:
         engine = LLMEngine(model, max_num_seqs=max(1, len(prompts)), eos_token_id=eos,
                            # --logprobs 0 still needs the kernel, hence an engine with N >= 1
-                           max_logprobs=0 if args.logprobs is None else max(1, args.logprobs))
+                           max_logprobs=0 if args.logprobs is None else max(1, args.logprobs),
+                           penalties=params.has_penalties)  # the state only when a flag differs from its default
         per = [SamplingParams(**{**params.__dict__, "seed": seed + i}) for i in range(len(prompts))]
         if args.logprobs is None:
             outputs = engine.generate(prompts, per)

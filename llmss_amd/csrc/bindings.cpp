@@ -42,6 +42,11 @@ void launch_token_logprobs(const void* logits, int64_t ld, bool fp32, int B, int
                            int64_t ld_top, void* top_ids, int64_t ld_ids, void* pack, int64_t ldp, hipStream_t st);
 void launch_logprobs_combine(const void* pack, int64_t ldp, int B, int groups, int N, void* lp, int64_t ld_lp,
                              void* top_lp, int64_t ld_top, void* top_ids, int64_t ld_ids, hipStream_t st);
+void launch_apply_penalties(const void* logits, int64_t ld, void* out, int64_t ldo, bool fp32, int B, int W, int lo,
+                            int vocab, void* state, int64_t lds, int nslots, const void* slots,
+                            const void* new_tokens, const void* rep, const void* pres, const void* freq, hipStream_t st);
+void launch_penalty_reset(void* state, int64_t lds, int nslots, int width, const void* slots, int R, const void* cu,
+                          int ntok, const void* tokens, const void* words, hipStream_t st);
 void launch_attn_extend(const void* q, int64_t q_stride, const void* k_cache, const void* v_cache,
                         const void* block_tables, int max_blocks, const void* cu_q, const void* ctx_lens, void* out,
                         int64_t out_stride, int B, int max_qlen, int nh, int nkv, int D, int bs, float scale,
@@ -140,6 +145,16 @@ PYBIND11_MODULE(_C, m) {
   m.def("logprobs_combine", [](uintptr_t pack, int64_t ldp, int B, int groups, int N, uintptr_t lp, int64_t ld_lp,
                                uintptr_t tlp, int64_t ld_top, uintptr_t tid, int64_t ld_ids, uintptr_t st) {
     launch_logprobs_combine(CP(pack), ldp, B, groups, N, P(lp), ld_lp, P(tlp), ld_top, P(tid), ld_ids, S(st));
+  });
+  m.def("apply_penalties", [](uintptr_t lg, int64_t ld, uintptr_t out, int64_t ldo, bool fp32, int B, int W, int lo,
+                              int vocab, uintptr_t state, int64_t lds, int nslots, uintptr_t slots, uintptr_t tok,
+                              uintptr_t rep, uintptr_t pres, uintptr_t freq, uintptr_t st) {
+    launch_apply_penalties(CP(lg), ld, P(out), ldo, fp32, B, W, lo, vocab, P(state), lds, nslots, CP(slots), CP(tok),
+                           CP(rep), CP(pres), CP(freq), S(st));
+  });
+  m.def("penalty_reset", [](uintptr_t state, int64_t lds, int nslots, int width, uintptr_t slots, int R, uintptr_t cu,
+                            int ntok, uintptr_t tokens, uintptr_t words, uintptr_t st) {
+    launch_penalty_reset(P(state), lds, nslots, width, CP(slots), R, CP(cu), ntok, CP(tokens), CP(words), S(st));
   });
   m.def("attn_extend", [](uintptr_t q, int64_t qs, uintptr_t kc, uintptr_t vc, uintptr_t bt, int maxb, uintptr_t cu,
                           uintptr_t cl, uintptr_t out, int64_t os, int B, int maxq, int nh, int nkv, int D, int bs,

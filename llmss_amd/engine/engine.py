@@ -93,15 +93,19 @@ class _DecodeBuffers:
     the host fills step t+1's set while step t's copy may still be queued, so a set is rewritten
     only after the step that used it has been collected. Token ids come back through two pinned
     output buffers for the same reason. ``max_logprobs`` N > 0 adds the log-probability outputs: ``lp_f`` [max_b, 1 + N]
-    fp32 (the sampled token's, then the top N) and ``lp_i`` [max_b, N] int32 (their ids) with two pinned host sets."""
+    fp32 (the sampled token's, then the top N) and ``lp_i`` [max_b, N] int32 (their ids) with two pinned host sets.
+    ``penalties`` appends ``pslot`` (i32, after the block tables) and ``rep`` / ``pres`` / ``freq`` (f32, after top_p) to
+    the staging blob - without it every offset is as before - and keeps the penalised logits, one static buffer per
+    logits width (``pen_out``)."""
 
-    def __init__(self, max_b: int, max_blocks: int, device, max_logprobs: int = 0):
+    def __init__(self, max_b: int, max_blocks: int, device, max_logprobs: int = 0, penalties: bool = False):
         B, MB = max_b, max_blocks
         self.max_b, self.max_blocks = B, MB
+        self.penalties = bool(penalties)
         pin = torch.cuda.is_available() and device.type == "cuda"
-        self.o32 = 4 * B * 8  # ids|pos|slots|seeds (i64) | ctx|topk|bt (i32) | temp|topp (f32)
-        self.of32 = self.o32 + (2 * B + B * MB) * 4
-        nbytes = self.of32 + 2 * B * 4
+        self.o32 = 4 * B * 8  # ids|pos|slots|seeds (i64) | ctx|topk|bt[|pslot] (i32) | temp|topp[|rep|pres|freq] (f32)
+        self.of32 = self.o32 + (2 * B + B * MB + (B if penalties else 0)) * 4
+        nbytes = self.of32 + (5 if penalties else 2) * B * 4
         self.h = [torch.zeros(nbytes, dtype=torch.uint8, pin_memory=pin) for _ in range(2)]
         self.d = torch.zeros(nbytes, dtype=torch.uint8, device=device)
         self.d_i64 = self.d[:self.o32].view(torch.int64)
@@ -111,8 +115,12 @@ class _DecodeBuffers:
         self.h_out = [torch.zeros(max_b, dtype=torch.int64, pin_memory=pin) for _ in range(2)]
         self.ids, self.pos, self.slots, self.seeds = (self.d_i64[i * B:(i + 1) * B] for i in range(4))
         self.ctx, self.topk = self.d_i32[:B], self.d_i32[B:2 * B]
-        self.bt = self.d_i32[2 * B:].view(B, max_blocks)
-        self.temp, self.topp = self.d_f32[:B], self.d_f32[B:]
+        self.bt = self.d_i32[2 * B:2 * B + B * MB].view(B, max_blocks)
+        self.temp, self.topp = self.d_f32[:B], self.d_f32[B:2 * B]
+        if penalties:
+            self.pslot = self.d_i32[2 * B + B * MB:]
+            self.rep, self.pres, self.freq = (self.d_f32[i * B:(i + 1) * B] for i in (2, 3, 4))
+            self._pen_out = {}
         N = self.max_logprobs = max_logprobs
         if N > 0:
             self.lp_f = torch.zeros(max_b, 1 + N, dtype=torch.float32, device=device)
@@ -126,9 +134,18 @@ class _DecodeBuffers:
             return None
         return self.lp_f[:b, 0], self.lp_f[:b, 1:], self.lp_i[:b]
 
-    def fill(self, k, b_pad, ids, pos, slots, seeds, ctx, topk, bt, temp, topp):
+    def pen_out(self, b: int, like: torch.Tensor) -> torch.Tensor:
+        """The static buffer the penalised copy of the [b, width] logits ``like`` goes to. Made at the first (warm-up)
+        call for a width and kept for the buffers' lifetime: captured graphs write and read it."""
+        key = (like.shape[1], like.dtype)
+        if key not in self._pen_out:
+            self._pen_out[key] = torch.zeros(self.max_b, like.shape[1], dtype=like.dtype, device=like.device)
+        return self._pen_out[key][:b]
+
+    def fill(self, k, b_pad, ids, pos, slots, seeds, ctx, topk, bt, temp, topp, pen=None):
         """Stage one step's inputs in set k and copy them to the device. ``ids=None``: the input ids
-        are the previous step's sampled tokens, copied on the device (same rows)."""
+        are the previous step's sampled tokens, copied on the device (same rows). ``pen``: the rows' (penalty slot,
+        repetition, presence, frequency) arrays; padded rows get slot -1."""
         n = len(pos)
         B, MB = self.max_b, self.max_blocks
         h = self.h[k]
@@ -143,13 +160,20 @@ class _DecodeBuffers:
         hi32[n:b_pad] = 0
         hi32[B:B + n] = topk
         hi32[B + n:B + b_pad] = 1
-        btv = hi32[2 * B:].reshape(B, MB)
+        btv = hi32[2 * B:2 * B + B * MB].reshape(B, MB)
         btv[:n, :bt.shape[1]] = bt
         btv[n:b_pad] = 0
         hf[:n] = temp
         hf[n:b_pad] = 0
         hf[B:B + n] = topp
         hf[B + n:B + b_pad] = 1
+        if self.penalties:
+            ps = hi32[2 * B + B * MB:]
+            ps[:b_pad] = -1
+            if pen is not None:
+                ps[:n] = pen[0]
+                for j, arr in enumerate(pen[1:], start=2):
+                    hf[j * B:j * B + n] = arr
         self.d.copy_(h, non_blocking=True)
         if ids is None:
             self.ids[:n].copy_(self.out[:n])
@@ -161,8 +185,12 @@ class LLMEngine:
                  kv_fraction: float = 0.9, use_graphs: Optional[bool] = None, eos_token_id: Optional[int] = None,
                  graph_buckets: Optional[Sequence[int]] = None, check_tokens: Optional[bool] = None,
                  autotune: Optional[bool] = None, prefill_chunk: Optional[int] = None,
-                 kv_dtype: Optional[str] = None, max_logprobs: int = 0):
+                 kv_dtype: Optional[str] = None, max_logprobs: int = 0, penalties: bool = False):
         self.model = model
+        # launch-time opt-in: True keeps every running sequence's token history on the device (one int32 word per
+        # slot and token) and runs the penalty launch between the LM head and the sampler; False leaves graphs,
+        # buffers and steps as they are and rejects requests that ask for a penalty
+        self.penalties = bool(penalties)
         # launch-time opt-in: N > 0 computes, after every sampler call, the sampled token's log-probability and the
         # N most likely tokens (ops.token_logprobs); 0 leaves graphs, buffers and steps as they are
         if not (isinstance(max_logprobs, int) and 0 <= max_logprobs <= MAX_TOP_LOGPROBS):
@@ -186,6 +214,14 @@ class LLMEngine:
         # every rank runs its own scheduler on the same request stream, so the KV pool (admission,
         # preemption) must be identical everywhere: each rank sizes it from its own free HBM, then all
         # take the minimum
+        # penalty state before the KV cache is sized, so that _auto_blocks sees the memory it takes
+        self.pen_state = None
+        self._pen_free: List[int] = list(range(max_num_seqs - 1, -1, -1))  # free state rows (pop() takes the lowest)
+        self._pen_slot: Dict[int, int] = {}  # request id -> state row; holders are always running sequences
+        if self.penalties:
+            if model.dtype not in (torch.bfloat16, torch.float32):
+                raise ValueError(f"penalties need bfloat16 or float32 logits, the model computes {model.dtype}")
+            self.pen_state = torch.zeros(max_num_seqs, self.cfg.vocab_size, dtype=torch.int32, device=self.device)
         self.num_blocks = self.tp.all_reduce_int(num_blocks or self._auto_blocks(kv_fraction), "min")
         self.kv = model.allocate_kv_cache(self.num_blocks, block_size)
         # chunked prefill: prompts are cut to fit the per-step token budget and ride along with the
@@ -210,6 +246,8 @@ class LLMEngine:
         self.check_tokens = check_tokens if check_tokens is not None else os.environ.get("LLMSS_CHECK_TOKENS") == "1"
         self.stats = {"steps": 0, "prefill_steps": 0, "decode_steps": 0, "tokens": 0, "prefill_tokens": 0,
                       "preemptions": 0, "decode_time_s": 0.0, "prefill_time_s": 0.0, "peak_live_kv_blocks": 0}
+        if self.penalties:
+            self.stats["penalty_state_bytes"] = self.pen_state.numel() * 4
         self.timer = PhaseTimer()  # LLMSS_TIMING=1: HIP-event device time per phase; LLMSS_ROCTX=1: roctx ranges
         self._host_prof = self.timer.enabled  # LLMSS_TIMING=1 also records host-side time per engine phase
         self.use_graphs = self.is_gpu if use_graphs is None else (use_graphs and self.is_gpu)
@@ -235,7 +273,7 @@ class LLMEngine:
         # (column-chunked all-reduces beside the next chunk's GEMM)
         self.decode_schedule: Dict[int, str] = {}
         self.tp.check_consistent("LLMEngine", self.fingerprint())
-        self.buf = _DecodeBuffers(self.buckets[-1], self.max_blocks, self.device, self.max_logprobs) \
+        self.buf = _DecodeBuffers(self.buckets[-1], self.max_blocks, self.device, self.max_logprobs, self.penalties) \
             if self.is_gpu else None
         if self.is_gpu:
             _hip_ops.reserve_workspace(self.device, 64 << 20)
@@ -343,6 +381,7 @@ class LLMEngine:
                 "buckets": list(self.buckets), "graphs": bool(self.use_graphs),
                 "async_decode": self.async_decode, "eos": self.eos, "prefill_chunk": self.prefill_chunk, "window": self.window,
                 "dist_sampling": self.dist_sampling, "max_logprobs": self.max_logprobs, "kv_fp8": bool(self.model.kv_fp8),
+                "penalties": self.penalties,
                 "overlap_rows": self.model.overlap_rows, "bucket_bytes": self.model.bucket_bytes,
                 "tbo_min": self.model.tbo_min, "graph_keys": sorted(self.graphs),
                 "decode_schedule": sorted(self.decode_schedule.items()), "rsag_mode": self.model.rsag_mode,
@@ -495,6 +534,11 @@ class LLMEngine:
             if params.logprobs > self.max_logprobs:
                 raise ValueError(f"logprobs = {params.logprobs} exceeds the engine's max_logprobs = "
                                  f"{self.max_logprobs}")
+        if params.has_penalties:
+            params.validate()
+            if not self.penalties:
+                raise ValueError("a repetition, presence or frequency penalty was requested but the engine was "
+                                 "launched without them (LLMEngine(penalties=True), server --penalties)")
         prompt = list(int(t) for t in prompt_ids)
         if not prompt:
             raise ValueError("empty prompt")
@@ -517,6 +561,7 @@ class LLMEngine:
             self.sched.abort(rid)
             r = self.requests[rid]
             r.finished, r.finish_reason = True, "abort"
+            self._pen_release(rid)
             if self._pending:  # rows of in-flight decode steps: no speculative successor may touch it
                 self._aborted.add(rid)
 
@@ -529,6 +574,59 @@ class LLMEngine:
             del self.requests[r.id]
             self._aborted.discard(r.id)
         return done
+
+    # -------------------------------------------------------------------------- penalties
+    def _pen_release(self, rid: int):
+        """Give a request's state row back (finish, abort, preemption). A decode step still in flight may go on
+        registering tokens into the row: the next holder's penalty_reset rebuilds it whole, later on the same stream."""
+        s = self._pen_slot.pop(rid, None)
+        if s is not None:
+            self._pen_free.append(s)
+
+    def _pen_arrays(self, reqs: List[Request]):
+        """(slot, repetition, presence, frequency) rows of a step; slot -1 where the request holds no state row."""
+        return (np.array([self._pen_slot.get(r.id, -1) for r in reqs], dtype=np.int32),
+                np.array([r.params.repetition_penalty for r in reqs], dtype=np.float32),
+                np.array([r.params.presence_penalty for r in reqs], dtype=np.float32),
+                np.array([r.params.frequency_penalty for r in reqs], dtype=np.float32))
+
+    def _pen_acquire(self, reqs: List[Request]) -> np.ndarray:
+        """Give every request of a sampling step that asks for penalties and holds no state row one, rebuilt in one
+        launch from its prompt (flag) and its output so far (counts): the step completes its known tokens for the
+        first time - the last chunk of its prompt, or of the re-prefill after a preemption (the scheduler hands a
+        last chunk of one token out as a decode row). Returns the mask of those rows: they register nothing in this
+        step, every other row registers its input token."""
+        fresh = np.zeros(len(reqs), dtype=bool)
+        rs, cu, toks, words = [], [0], [], []
+        for i, r in enumerate(reqs):
+            if r.id in self._pen_slot or not r.params.has_penalties:
+                continue
+            fresh[i] = True
+            self._pen_slot[r.id] = self._pen_free.pop()
+            t, w = ops.penalty_words(r.prompt_ids, r.output_ids)
+            rs.append(self._pen_slot[r.id])
+            toks.append(t)
+            words.append(w)
+            cu.append(cu[-1] + t.size)
+        if rs:
+            dev = self.device
+            ops.penalty_reset(self.pen_state, torch.tensor(rs, dtype=torch.int32).to(dev),
+                              torch.tensor(cu, dtype=torch.int32).to(dev),
+                              torch.from_numpy(np.concatenate(toks)).to(dev),
+                              torch.from_numpy(np.concatenate(words)).to(dev))
+        return fresh
+
+    def _pen_eager(self, reqs: List[Request]):
+        """Penalty inputs of an eager sampling step over ``reqs`` (_forward_sample's ``pen``), or None when no row
+        holds a state row (the launch would be a copy)."""
+        if not self.penalties:
+            return None
+        fresh = self._pen_acquire(reqs)
+        slot, rep, pres, freq = self._pen_arrays(reqs)
+        if not (slot >= 0).any():
+            return None
+        new = np.where(fresh, -1, np.array([r.last_id for r in reqs], dtype=np.int64))
+        return tuple(torch.from_numpy(a).to(self.device) for a in (slot, new, rep, pres, freq)) + (None,)
 
     # -------------------------------------------------------------------------- step
     def _sampling_arrays(self, reqs: List[Request]):
@@ -576,6 +674,8 @@ class LLMEngine:
             # the scheduler preempts its way out of a starved pool, so an idle step with work left is a bug
             raise RuntimeError(f"scheduler returned an idle step with {self.sched.num_waiting()} waiting and "
                                f"{self.sched.num_running()} running sequences")
+        for rid in batch.preempted.tolist():  # recomputed later: the re-prefill takes a state row again
+            self._pen_release(int(rid))
         if batch.kind != 0:
             self.stats["preemptions"] += len(batch.preempted)
             ids = batch.ids
@@ -643,6 +743,7 @@ class LLMEngine:
             else:
                 continue
             fins[i] = True
+            self._pen_release(r.id)
         self.sched.on_tokens(ids, fins)
         self._last_fins = fins
         self.stats["steps"] += 1
@@ -696,7 +797,7 @@ class LLMEngine:
             return []
         temp, topk, topp, seeds = self._sampling_arrays(reqs)
         tok = self._forward_sample(inp, *(torch.from_numpy(a).to(dev) for a in (temp, topk, topp, seeds)),
-                                   dist=self._dist_ok(temp, topk))
+                                   dist=self._dist_ok(temp, topk), pen=self._pen_eager(reqs))
         self._step_lps = self._lps_to_host()
         return tok.cpu().tolist()
 
@@ -704,11 +805,19 @@ class LLMEngine:
         """Sample this step from vocab-parallel candidates (no [B, V] logits all-gather)?"""
         return self.dist_sampling and ops.cand_ok(temp, topk)
 
-    def _forward_sample(self, inp: StepInput, temp, topk, topp, seeds, out=None, dist=False, lp_out=None):
+    def _penalise(self, logits, pen, lo, vocab):
+        """The penalty launch between the LM head and the sampler: ``pen`` = (slots, new tokens, repetition, presence,
+        frequency, static decode buffers or None). Out of place - the raw logits stay for the log-probabilities."""
+        slots, new, rep, pres, freq, buf = pen
+        out = buf.pen_out(logits.shape[0], logits) if buf is not None else None
+        return ops.apply_penalties(logits, self.pen_state, slots, new, rep, pres, freq, lo, vocab, out)
+
+    def _forward_sample(self, inp: StepInput, temp, topk, topp, seeds, out=None, dist=False, lp_out=None, pen=None):
         """Forward + LM head + sampler. ``dist``: each rank keeps its logit shard and only candidates
         are gathered (ops.sample_distributed); otherwise the [B, V] logits are all-gathered. With max_logprobs > 0
         a separate launch after the sampler reads the same logits and the sampled ids (ops.token_logprobs; on the
-        ``dist`` path per-shard packs, an all-gather and a combine) into ``lp_out`` or ``self._lps``."""
+        ``dist`` path per-shard packs, an all-gather and a combine) into ``lp_out`` or ``self._lps``. ``pen``: the
+        sampler reads the penalised copy of the logits (_penalise); the log-probabilities stay those of the raw ones."""
         m = self.model
         V = self.cfg.vocab_size
         N = self.max_logprobs
@@ -717,16 +826,18 @@ class LLMEngine:
             if inp.last_idx is not None:
                 h = h.index_select(0, inp.last_idx)
             local = m.local_logits(h)
-            tok = ops.sample_distributed(local, self.tp, m.vocab_lo, V, temp, topk, topp, seeds, out=out)
+            plocal = local if pen is None else self._penalise(local, pen, m.vocab_lo, V)
+            tok = ops.sample_distributed(plocal, self.tp, m.vocab_lo, V, temp, topk, topp, seeds, out=out)
             if N > 0:
                 self._lps = ops.token_logprobs_distributed(local, self.tp, m.vocab_lo, V, tok, N, out=lp_out)
             return tok
         logits = m(inp, self.kv)
         vocab = min(V, logits.shape[-1])
+        plogits = logits if pen is None else self._penalise(logits, pen, 0, vocab)
         if logits.is_cuda:
-            tok = _hip_ops.sample(logits, temp, topk, topp, seeds, vocab=vocab, out=out)
+            tok = _hip_ops.sample(plogits, temp, topk, topp, seeds, vocab=vocab, out=out)
         else:
-            tok = ops.sample(logits, temp, topk, topp, seeds, vocab=vocab)
+            tok = ops.sample(plogits, temp, topk, topp, seeds, vocab=vocab)
         if N > 0:
             self._lps = ops.token_logprobs(logits, vocab, tok, N, out=lp_out)
         return tok
@@ -738,12 +849,15 @@ class LLMEngine:
         lp, top, tids = self._lps
         return torch.cat([lp.view(-1, 1), top], dim=1).cpu().numpy(), tids.cpu().numpy()
 
-    def _decode_forward(self, b: int, buf: _DecodeBuffers, dist: bool = False):
+    def _decode_forward(self, b: int, buf: _DecodeBuffers, dist: bool = False, pnew=None):
         inp = StepInput(kind="decode", input_ids=buf.ids[:b], positions=buf.pos[:b], slots=buf.slots[:b],
                         block_tables=buf.bt[:b], ctx_lens=buf.ctx[:b], max_ctx=self.max_model_len,
                         decode_splits=self._splits(b), window=self.window)
+        # every decode step registers its input token before the penalties are applied
+        pen = (buf.pslot[:b], buf.ids[:b] if pnew is None else pnew, buf.rep[:b], buf.pres[:b], buf.freq[:b], buf) \
+            if self.penalties else None
         self._forward_sample(inp, buf.temp[:b], buf.topk[:b], buf.topp[:b], buf.seeds[:b], out=buf.out[:b],
-                             dist=dist, lp_out=buf.lp_out(b))
+                             dist=dist, lp_out=buf.lp_out(b), pen=pen)
 
     def _decode_cpu(self, batch, reqs: List[Request]) -> List[int]:
         ids = np.array([r.last_id for r in reqs], dtype=np.int64)
@@ -753,7 +867,8 @@ class LLMEngine:
                         block_tables=torch.from_numpy(batch.block_table.astype(np.int32)),
                         ctx_lens=torch.from_numpy(batch.ctx_lens.astype(np.int32)), max_ctx=self.max_model_len,
                         window=self.window)
-        tok = self._forward_sample(inp, temp, topk, topp, seeds, dist=self._dist_ok(temp, topk))
+        tok = self._forward_sample(inp, temp, topk, topp, seeds, dist=self._dist_ok(temp, topk),
+                                   pen=self._pen_eager(reqs))
         self._step_lps = self._lps_to_host()
         return tok.tolist()
 
@@ -762,9 +877,10 @@ class LLMEngine:
         """Decode step record for a scheduled batch. Per-request constants are reused from the last
         collected step when the running set is unchanged (every member then got one token)."""
         last = self._last_rec
+        fresh = self._pen_acquire(reqs) if self.penalties else None
         if last is not None and last["ids"].shape == ids.shape and np.array_equal(last["ids"], ids) \
-                and last["keep"].all():
-            c = {k: last[k] for k in ("temp", "topk", "topp", "seed", "maxnew")}
+                and last["keep"].all() and not (fresh is not None and fresh.any()):
+            c = {k: last[k] for k in ("temp", "topk", "topp", "seed", "maxnew") + (("pen",) if self.penalties else ())}
             c["nout"] = last["nout"] + 1
             c["last"] = last["tokens"]
         else:
@@ -775,6 +891,10 @@ class LLMEngine:
                  "maxnew": np.array([r.params.max_new_tokens for r in reqs], dtype=np.int64),
                  "nout": np.array([len(r.output_ids) for r in reqs], dtype=np.int64),
                  "last": np.array([r.last_id for r in reqs], dtype=np.int64)}
+            if self.penalties:
+                c["pen"] = self._pen_arrays(reqs)
+                if fresh.any():  # rows whose reset covers their input token: this step registers nothing for them
+                    c["pnew"] = np.where(fresh, -1, c["last"])
         c.update(ids=ids, reqs=reqs, n=len(reqs), pos=batch.positions, ctx=batch.ctx_lens.astype(np.int32),
                  slots=batch.slots, bt=batch.block_table, keep=np.ones(len(reqs), dtype=bool))
         c["dist"] = self._dist_ok(c["temp"], c["topk"])
@@ -790,17 +910,20 @@ class LLMEngine:
         with self.timer.phase("decode"):
             buf.fill(k, b, None if device_ids else rec.pop("last"), rec["pos"], rec["slots"],
                      step_seeds(rec["seed"], rec["nout"]), rec["ctx"], rec["topk"], rec["bt"], rec["temp"],
-                     rec["topp"])
+                     rec["topp"], pen=rec.get("pen"))
             key = (b, bool(rec["dist"]))
             if self._host_prof:
                 # was the GPU already idle (every earlier step done) when this step was launched?
                 idle = bool(self._pending) and self._pending[-1]["ev"].query()
                 self.stats["host_late_launches"] = self.stats.get("host_late_launches", 0) + int(idle)
                 t_r = time.perf_counter()
-            if self.use_graphs and key in self.graphs:
+            pnew = rec.pop("pnew", None)
+            if self.use_graphs and key in self.graphs and pnew is None:
                 self.graphs[key].replay()
             else:
-                self._decode_forward(b, buf, dist=key[1])
+                if pnew is not None:  # not the input ids: an eager step with its own tokens to register
+                    pnew = torch.from_numpy(np.concatenate([pnew, np.full(b - n, -1, dtype=np.int64)])).to(self.device)
+                self._decode_forward(b, buf, dist=key[1], pnew=pnew)
             if self._host_prof:
                 self.stats["host_replay_s"] = self.stats.get("host_replay_s", 0.0) + time.perf_counter() - t_r
             buf.h_out[k][:n].copy_(buf.out[:n], non_blocking=True)
@@ -849,6 +972,8 @@ class LLMEngine:
         rec["keep"] = alive
         if dead.any():
             rec["topk"] = np.where(alive, cur["topk"], 1).astype(np.int32)
+        if self.penalties:  # dead rows hold no slot: their row of the state may already be another sequence's
+            rec["pen"] = (np.where(alive, cur["pen"][0], -1).astype(np.int32),) + tuple(cur["pen"][1:])
         self._launch_decode(rec, device_ids=True)
 
     def _collect_decode(self):
@@ -908,6 +1033,8 @@ class LLMEngine:
         buf.d_i32.zero_()
         buf.topk.fill_(1)
         buf.d_f32.zero_()
+        if self.penalties:
+            buf.pslot.fill_(-1)  # padded rows hold no penalty slot: the launch copies them
         modes = self._decode_modes()
         # warm-up passes (lazy allocations, first launches). Native RCCL: with real collectives, so each
         # algorithm's lazy peer connection happens here and not inside the capture. torch's RCCL process

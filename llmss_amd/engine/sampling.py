@@ -16,6 +16,8 @@ parameters reproduce exactly.
 from __future__ import annotations
 
 import itertools
+import math
+import numbers
 import os
 from dataclasses import dataclass, field
 from typing import List, Optional
@@ -25,6 +27,10 @@ import numpy as np
 _seed_counter = itertools.count(int.from_bytes(os.urandom(4), "little"))
 MASK64 = (1 << 64) - 1
 MAX_TOP_LOGPROBS = 20  # most alternatives per generated position a request may ask for (csrc/logprobs.hip)
+
+
+def _is_number(v) -> bool:
+    return isinstance(v, numbers.Real) and not isinstance(v, bool)
 
 
 @dataclass
@@ -42,6 +48,17 @@ class SamplingParams:
     # likely tokens at each generated position (logit descending, ties by ascending id). Needs an engine launched
     # with max_logprobs >= n.
     logprobs: Optional[int] = None
+    # repetition control, applied to the logits before temperature, top-k and top-p (csrc/penalties.hip). A token seen
+    # in the prompt or the output has its logit x replaced by x / repetition_penalty (x > 0) or x * repetition_penalty
+    # (Hugging Face); a token that occurs c > 0 times in the output then loses frequency_penalty * c +
+    # presence_penalty (OpenAI). Anything but the defaults needs an engine launched with penalties=True.
+    repetition_penalty: float = 1.0
+    presence_penalty: float = 0.0
+    frequency_penalty: float = 0.0
+
+    @property
+    def has_penalties(self) -> bool:
+        return not (self.repetition_penalty == 1.0 and self.presence_penalty == 0.0 and self.frequency_penalty == 0.0)
 
     def validate(self) -> "SamplingParams":
         """Reference validation (generate.py:37-40)."""
@@ -56,6 +73,13 @@ class SamplingParams:
         lp = self.logprobs
         if lp is not None and not (isinstance(lp, int) and not isinstance(lp, bool) and 0 <= lp <= MAX_TOP_LOGPROBS):
             raise ValueError(f"Value of logprobs should be None or an integer in 0..{MAX_TOP_LOGPROBS}.")
+        r = self.repetition_penalty
+        if not (_is_number(r) and math.isfinite(r) and r > 0):
+            raise ValueError("Value of repetition_penalty should be a finite number above 0.")
+        for name in ("presence_penalty", "frequency_penalty"):
+            v = getattr(self, name)
+            if not (_is_number(v) and math.isfinite(v) and -2.0 <= v <= 2.0):
+                raise ValueError(f"Value of {name} should be a finite number in [-2, 2].")
         return self
 
     def resolved_seed(self) -> int:

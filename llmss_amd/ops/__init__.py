@@ -14,7 +14,7 @@ from . import reference as ref
 
 __all__ = ["add_norm", "embed", "rope_cache", "attn_prefill", "attn_decode", "attn_extend", "linear", "sample", "quant_fp8_rows",
            "rope_tables", "glu_interleave", "glu_split", "cross_entropy", "token_logprobs",
-           "token_logprobs_distributed", "MAX_TOP_LOGPROBS"]
+           "token_logprobs_distributed", "MAX_TOP_LOGPROBS", "apply_penalties", "penalty_reset", "penalty_words"]
 
 rope_tables = ref.rope_tables
 glu_interleave = ref.glu_interleave
@@ -188,6 +188,25 @@ def token_logprobs_distributed(local, tp, lo, V, tokens, N, out=None, shards=1):
         return h.token_logprobs_combine(allp, N, out=out)
     allp = tp.all_gather_last_dim(ref.token_logprobs_partial(local, lo, V, tokens, N, shards=shards))
     return _lp_out(ref.token_logprobs_combine(allp, N), out)
+
+
+penalty_words = ref.penalty_words
+
+
+def apply_penalties(logits, state, slots, new_tokens, rep, pres, freq, lo=0, vocab=None, out=None):
+    """Repetition / presence / frequency penalties from device-resident token history, out of place; registers
+    ``new_tokens`` in ``state`` first (ops/reference.py apply_penalties is the definition, csrc/penalties.hip the
+    GPU kernel)."""
+    if logits.is_cuda:
+        return _hip().apply_penalties(logits, state, slots, new_tokens, rep, pres, freq, lo, vocab, out)
+    return ref.apply_penalties(logits, state, slots, new_tokens, rep, pres, freq, lo, vocab, out)
+
+
+def penalty_reset(state, slots, cu, tokens, words):
+    """(Re)build whole penalty state rows from each sequence's distinct tokens and finished words."""
+    if state.is_cuda:
+        return _hip().penalty_reset(state, slots, cu, tokens, words)
+    return ref.penalty_reset(state, slots, cu, tokens, words)
 
 
 def quant_fp8_rows(w):

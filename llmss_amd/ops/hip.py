@@ -914,3 +914,84 @@ def token_logprobs_combine(pack, N, out=None):
     lib().logprobs_combine(pack.data_ptr(), pack.stride(0), B, groups, N, lp.data_ptr(), lp.stride(0) if B else 1,
                            top.data_ptr(), top.stride(0), ids.data_ptr(), ids.stride(0), _stream())
     return lp, top, ids
+
+
+# ---------------------------------------------------------------------------------------- penalties
+def _pen_vec(t, dt, n, device, name):
+    _check(torch.is_tensor(t) and t.dtype == dt and t.device == device and t.dim() == 1 and t.shape[0] == n
+           and t.is_contiguous(), f"{name} must be a contiguous {dt} [{n}] tensor on {device}")
+
+
+def _pen_state(state, name="state"):
+    _check(torch.is_tensor(state) and state.is_cuda and state.dtype == torch.int32 and state.dim() == 2
+           and state.stride(1) == 1, f"{name} must be [S, vocab] int32 GPU rows")
+    _check(state.device.index == torch.cuda.current_device(),
+           f"{name} is on {state.device} but the current device is cuda:{torch.cuda.current_device()}")
+    _check(state.shape[0] <= 1 or state.stride(0) >= state.shape[1], f"{name} rows overlap")
+
+
+def _overlap(a, b) -> bool:
+    """Do the address ranges of two row-strided 2-D tensors intersect?"""
+    def span(t):
+        n = (t.shape[0] - 1) * t.stride(0) + t.shape[1] if t.numel() else 0
+        return t.data_ptr(), t.data_ptr() + n * t.element_size()
+    a0, a1 = span(a)
+    b0, b1 = span(b)
+    return a0 < b1 and b0 < a1
+
+
+def apply_penalties(logits, state, slots, new_tokens, rep, pres, freq, lo=0, vocab=None, out=None):
+    """Repetition / presence / frequency penalties over ``logits`` [B, W] (bf16 / fp32, any row stride) whose column
+    j is global token ``lo + j``, written out of place into ``out`` (csrc/penalties.hip; ops/reference.py
+    apply_penalties is the definition). Row b with ``slots[b]`` >= 0 first registers ``new_tokens[b]`` (>= 0) as one
+    more output occurrence in its ``state`` row. The rows of one call must hold different slots."""
+    _check(torch.is_tensor(logits) and logits.is_cuda and logits.dim() == 2 and (logits.shape[1] <= 1 or
+                                                                                logits.stride(1) == 1),
+           "logits must be [B, W] GPU rows")
+    _check(logits.device.index == torch.cuda.current_device(),
+           f"logits is on {logits.device} but the current device is cuda:{torch.cuda.current_device()}")
+    _check(logits.dtype in (torch.bfloat16, torch.float32), f"logits must be bfloat16 or float32, got {logits.dtype}")
+    B, W = logits.shape
+    _check(B <= 1 or logits.stride(0) >= W, "logits rows overlap")
+    _pen_state(state)
+    _check(state.device == logits.device, "state and logits are on different devices")
+    vocab = state.shape[1] if vocab is None else int(vocab)
+    lo = int(lo)
+    _check(lo >= 0 and 0 <= vocab <= state.shape[1], f"need lo >= 0 and 0 <= vocab <= state.shape[1] = "
+                                                      f"{state.shape[1]}, got lo = {lo}, vocab = {vocab}")
+    _check(B <= 65535 and lo + W < 2 ** 31, "too many rows or columns")
+    _pen_vec(slots, torch.int32, B, logits.device, "slots")
+    _pen_vec(new_tokens, torch.int64, B, logits.device, "new_tokens")
+    for t, nm in ((rep, "rep"), (pres, "pres"), (freq, "freq")):
+        _pen_vec(t, torch.float32, B, logits.device, nm)
+    if out is None:
+        out = torch.empty(B, W, dtype=logits.dtype, device=logits.device)
+    _check(torch.is_tensor(out) and out.dtype == logits.dtype and out.device == logits.device
+           and tuple(out.shape) == (B, W) and (W <= 1 or out.stride(1) == 1),
+           f"out must be a {logits.dtype} [{B}, {W}] tensor with contiguous rows on {logits.device}")
+    _check(B <= 1 or out.stride(0) >= W, "out rows overlap")
+    _check(not _overlap(out, logits), "out must not alias logits: the raw logits are kept")
+    lib().apply_penalties(logits.data_ptr(), logits.stride(0), out.data_ptr(), out.stride(0),
+                          logits.dtype == torch.float32, B, W, lo, vocab, state.data_ptr(), state.stride(0),
+                          state.shape[0], slots.data_ptr(), new_tokens.data_ptr(), rep.data_ptr(), pres.data_ptr(),
+                          freq.data_ptr(), _stream())
+    return out
+
+
+def penalty_reset(state, slots, cu, tokens, words):
+    """(Re)build the state rows ``slots`` [R] int32 (-1: skip) in one launch: row i becomes zero except its distinct
+    ``tokens[cu[i]:cu[i + 1]]`` (int64), which get ``words[cu[i]:cu[i + 1]]`` (int32). ``cu`` [R + 1] int32."""
+    _pen_state(state)
+    dev = state.device
+    _check(torch.is_tensor(slots) and slots.dim() == 1, "slots must be 1-D")
+    R = slots.shape[0]
+    _check(R <= 65535, "too many rows")
+    _pen_vec(slots, torch.int32, R, dev, "slots")
+    _pen_vec(cu, torch.int32, R + 1, dev, "cu")
+    _check(torch.is_tensor(tokens) and tokens.dim() == 1, "tokens must be 1-D")
+    n = tokens.shape[0]
+    _pen_vec(tokens, torch.int64, n, dev, "tokens")
+    _pen_vec(words, torch.int32, n, dev, "words")
+    lib().penalty_reset(state.data_ptr(), state.stride(0), state.shape[0], state.shape[1], slots.data_ptr(), R,
+                        cu.data_ptr(), n, tokens.data_ptr(), words.data_ptr(), _stream())
+    return state

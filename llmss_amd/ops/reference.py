@@ -595,3 +595,65 @@ def cross_entropy(logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
 
 def softmax_scale(D: int) -> float:
     return 1.0 / math.sqrt(D)
+
+
+# ------------------------------------------------------------------------------------ penalties
+PENALTY_PROMPT_BIT = -(1 << 31)  # bit 31 of an int32 state word: the token occurs in the prompt; bits 0..30: output count
+
+
+def penalty_words(prompt_ids, output_ids):
+    """A sequence's distinct tokens (int64, ascending) and their finished state words (int32) for ``penalty_reset``."""
+    p = np.unique(np.asarray(prompt_ids, dtype=np.int64))
+    o, c = np.unique(np.asarray(output_ids, dtype=np.int64), return_counts=True)
+    toks = np.union1d(p, o)
+    words = np.zeros(toks.size, dtype=np.uint32)
+    words[np.searchsorted(toks, p)] = 1 << 31
+    words[np.searchsorted(toks, o)] |= c.astype(np.uint32)
+    return toks, words.view(np.int32)
+
+
+def apply_penalties(logits, state, slots, new_tokens, rep, pres, freq, lo: int = 0, vocab=None, out=None):
+    """Repetition / presence / frequency penalties (GPU ``apply_penalties``, csrc/penalties.hip). Row b with slot
+    ``slots[b]`` >= 0 first registers ``new_tokens[b]`` (>= 0) as one more output occurrence in its ``state`` row
+    [vocab] int32 (bit 31: in the prompt, bits 0..30: output count), then for column j = global token lo + j < vocab,
+    in fp32: seen -> x > 0 ? x / rep : x * rep; count c > 0 -> x - (freq * c + pres); one rounding to the logits'
+    dtype. Rows with slot -1, columns past ``vocab`` and unseen tokens are copied. Written out of place."""
+    B, W = logits.shape
+    vocab = state.shape[1] if vocab is None else int(vocab)
+    if out is None:
+        out = torch.empty(B, W, dtype=logits.dtype, device=logits.device)
+    out.copy_(logits)
+    n = max(0, min(W, vocab - lo))
+    for b in range(B):
+        s = int(slots[b])
+        if s < 0:
+            continue
+        t = int(new_tokens[b])
+        if 0 <= t < vocab:
+            state[s, t] += 1
+        if n == 0:
+            continue
+        w = state[s, lo:lo + n]
+        c = w & 0x7FFFFFFF
+        seen = w != 0
+        x = logits[b, :n].float()
+        r, p, f = (v[b].float() for v in (rep, pres, freq))
+        x = torch.where(seen, torch.where(x > 0, x / r, x * r), x)
+        x = torch.where(c > 0, x - (f * c.float() + p), x)
+        out[b, :n] = torch.where(seen, x.to(out.dtype), logits[b, :n])
+    return out
+
+
+def penalty_reset(state, slots, cu, tokens, words):
+    """(Re)build whole state rows: row ``slots[i]`` (>= 0) becomes zero except ``tokens[cu[i]:cu[i + 1]]`` (distinct),
+    which get ``words[cu[i]:cu[i + 1]]``."""
+    for i in range(slots.shape[0]):
+        s = int(slots[i])
+        if s < 0:
+            continue
+        a, b = int(cu[i]), int(cu[i + 1])
+        state[s].zero_()
+        t = tokens[a:b].long()
+        ok = (t >= 0) & (t < state.shape[1])
+        state[s, t[ok]] = words[a:b][ok].to(state.dtype)
+    return state

@@ -51,7 +51,8 @@ def _build_pool():
     msg("GenerateRequest", [("prompt", S, 0), ("max_new_tokens", I32, 0), ("is_greedy", B, 0), ("temperature", FL, 0),
                             ("top_p", FL, 0), ("top_k", I32, 0), ("request_id", S, 0), ("seed", I64, 0),
                             ("prompt_token_ids", I32, 1), ("ignore_eos", B, 0), ("return_logprobs", B, 0),
-                            ("top_logprobs", I32, 0)])
+                            ("top_logprobs", I32, 0), ("repetition_penalty", FL, 0), ("presence_penalty", FL, 0),
+                            ("frequency_penalty", FL, 0)])
     msg("TopLogprobs", [("token_ids", I32, 1), ("logprobs", FL, 1)])
     msg("GenerateResponse", [("prompt", S, 0), ("continuation", S, 0), ("request_id", S, 0), ("token_ids", I32, 1),
                              ("finish_reason", S, 0), ("ttft_s", FL, 0), ("e2e_s", FL, 0), ("token_logprobs", FL, 1),
@@ -94,9 +95,17 @@ def _logprob_fields(token_logprobs, top_logprobs) -> dict:
             "top_logprobs": [_top_msg([tuple(p) for p in t]) for t in top_logprobs or []]}
 
 
-def _params(req, max_logprobs: Optional[int] = None):
+def _penalty_fields(req) -> dict:
+    """The request's penalties as SamplingParams / protocol.Request fields; proto3 floats default to 0, so
+    repetition_penalty == 0 means 1.0 (as temperature == 0 means 1.0)."""
+    return {"repetition_penalty": float(req.repetition_penalty) or 1.0,
+            "presence_penalty": float(req.presence_penalty), "frequency_penalty": float(req.frequency_penalty)}
+
+
+def _params(req, max_logprobs: Optional[int] = None, penalties: Optional[bool] = None):
     """``max_logprobs``: the serving engine's launch-time limit when known - a log-probability request it cannot
-    serve is a ValueError here (INVALID_ARGUMENT), not a failed handle later."""
+    serve is a ValueError here (INVALID_ARGUMENT), not a failed handle later. ``penalties``: likewise whether the
+    engine was launched with penalties."""
     from ..engine.sampling import SamplingParams
 
     logprobs = int(req.top_logprobs) if req.return_logprobs else None
@@ -106,11 +115,14 @@ def _params(req, max_logprobs: Optional[int] = None):
         if logprobs > max_logprobs:
             raise ValueError(f"top_logprobs = {logprobs} exceeds the server's --max-logprobs {max_logprobs}")
 
+    pen = _penalty_fields(req)
+    if penalties is False and pen != {"repetition_penalty": 1.0, "presence_penalty": 0.0, "frequency_penalty": 0.0}:
+        raise ValueError("penalties are not enabled on this server (--penalties)")
     # proto3 scalars default to 0: 0 means "reference default" for max_new_tokens/temperature/top_p
     # (0 is invalid for them) and "disabled" for top_k (as in the reference CLI, generate.py:30).
     return SamplingParams(max_new_tokens=req.max_new_tokens or 20, is_greedy=req.is_greedy,
                           temperature=req.temperature or 1.0, top_p=req.top_p or 0.95, top_k=req.top_k,
-                          seed=req.seed or None, ignore_eos=req.ignore_eos, logprobs=logprobs).validate()
+                          seed=req.seed or None, ignore_eos=req.ignore_eos, logprobs=logprobs, **pen).validate()
 
 
 def add_servicer(server: grpc.Server, servicer) -> None:
@@ -293,6 +305,9 @@ class EngineServicer:
     def _max_logprobs(self):
         return getattr(getattr(self.driver, "engine", None), "max_logprobs", None)
 
+    def _penalties(self):
+        return getattr(getattr(self.driver, "engine", None), "penalties", None)
+
     def _prompt_ids(self, req):
         from ..utils.tokenizer import encode
 
@@ -302,7 +317,7 @@ class EngineServicer:
 
     async def Generate(self, req, ctx):
         try:
-            params = _params(req, self._max_logprobs())
+            params = _params(req, self._max_logprobs(), self._penalties())
         except ValueError as e:
             await ctx.abort(grpc.StatusCode.INVALID_ARGUMENT, str(e))
         loop = asyncio.get_running_loop()
@@ -331,7 +346,7 @@ class EngineServicer:
 
     async def GenerateStream(self, req, ctx):
         try:
-            params = _params(req, self._max_logprobs())
+            params = _params(req, self._max_logprobs(), self._penalties())
         except ValueError as e:
             await ctx.abort(grpc.StatusCode.INVALID_ARGUMENT, str(e))
         loop = asyncio.get_running_loop()
@@ -390,7 +405,7 @@ class BrokerServicer:
         return Request(prompt=req.prompt, max_new_tokens=req.max_new_tokens or 20, is_greedy=req.is_greedy,
                        temperature=req.temperature or 1.0, top_p=req.top_p or 0.95, top_k=req.top_k or 50,
                        request_id=rid, seed=req.seed or None, ignore_eos=req.ignore_eos, stream=stream,
-                       logprobs=int(req.top_logprobs) if req.return_logprobs else None,
+                       logprobs=int(req.top_logprobs) if req.return_logprobs else None, **_penalty_fields(req),
                        prompt_token_ids=list(req.prompt_token_ids) or None, deadline_s=deadline_s)
 
     def Generate(self, req, ctx):

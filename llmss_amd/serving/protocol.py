@@ -34,6 +34,10 @@ class Request(BaseModel):
     # log-probabilities of the raw model distribution: None none, 0 each generated token's, n also the n most likely
     # tokens per position (SamplingParams.logprobs; the serving engine needs --max-logprobs >= n)
     logprobs: Optional[int] = None
+    # repetition control (SamplingParams; the serving engine needs --penalties, else the reply is an error)
+    repetition_penalty: float = 1.0
+    presence_penalty: float = 0.0
+    frequency_penalty: float = 0.0
 
 
 class Response(BaseModel):
@@ -64,7 +68,8 @@ def parse_request(msg: str) -> Request:
 def to_sampling(req: Request) -> SamplingParams:
     return SamplingParams(max_new_tokens=req.max_new_tokens, is_greedy=req.is_greedy, temperature=req.temperature,
                           top_p=req.top_p, top_k=req.top_k, seed=req.seed, ignore_eos=req.ignore_eos,
-                          logprobs=req.logprobs).validate()
+                          logprobs=req.logprobs, repetition_penalty=req.repetition_penalty,
+                          presence_penalty=req.presence_penalty, frequency_penalty=req.frequency_penalty).validate()
 
 
 def dump_response(resp: Dict[str, Any]) -> str:
