@@ -48,6 +48,13 @@ def get_args(argv=None):
                         help="[-2, 2]: subtracted from the logit of every token generated so far")
     parser.add_argument("--frequency_penalty", type=float, default=0.0,
                         help="[-2, 2]: subtracted once per occurrence among the generated tokens")
+    parser.add_argument("--logit_bias", type=str, default=None,
+                        help='JSON object of token id -> bias in [-100, 100] added to its logit, e.g. \'{"50256": -100}\'')
+    parser.add_argument("--banned_token_ids", type=int, nargs="+", default=[], help="token ids that are never sampled")
+    parser.add_argument("--allowed_token_ids", type=int, nargs="+", default=[],
+                        help="the only token ids that are sampled")
+    parser.add_argument("--min_tokens", type=int, default=0,
+                        help="EOS is not sampled before this many tokens were generated")
     return parser.parse_args(argv)
 
 
@@ -78,6 +85,16 @@ def recompute_generate(model, prompts, params, eos, lp_out=None):
         ops.penalty_reset(state, torch.arange(len(prompts), dtype=torch.int32, device=dev),
                           torch.tensor(cu, dtype=torch.int32, device=dev),
                           *(torch.cat([torch.from_numpy(w[k]) for w in words]).to(dev) for k in (0, 1)))
+    edits = None
+    if params.has_constraints:  # every prompt has the same constraints: one slot
+        from llmss_amd.engine.sampling import MAX_TOKEN_EDITS, resolve_token_edits
+
+        if model.dtype not in (torch.bfloat16, torch.float32):
+            raise ValueError(f"token constraints need bfloat16 or float32 logits (--dtype bf16 | fp32), the model "
+                             f"computes {model.dtype}")
+        early, late, fill = resolve_token_edits(params, eos, V)
+        edits = [torch.from_numpy(a).unsqueeze(0).to(dev)
+                 for a in ops.pack_token_edits(early, late, fill, params.min_tokens, MAX_TOKEN_EDITS)]
     for step in range(params.max_new_tokens):
         live = [i for i in range(len(seqs)) if not done[i]]
         if not live:
@@ -102,6 +119,10 @@ def recompute_generate(model, prompts, params, eos, lp_out=None):
             plogits = ops.apply_penalties(logits, state, torch.tensor(live, dtype=torch.int32, device=dev),
                                           torch.tensor([outs[i][-1] if outs[i] else -1 for i in live], device=dev),
                                           *pen, 0, V)
+        if edits is not None:  # after the penalties, before the sampler
+            plogits = ops.apply_token_edits(plogits, *edits, torch.zeros(n, dtype=torch.int32, device=dev),
+                                            torch.tensor([len(outs[i]) for i in live], dtype=torch.int32, device=dev),
+                                            0, V)
         tok = ops.sample(plogits, temp, topk, topp, seeds, vocab=model.cfg.vocab_size)
         if lp_out is not None:
             nlp = params.logprobs
@@ -127,6 +148,10 @@ def main(argv=None):
     assert 0.0 < args.repetition_penalty < float("inf"), "Value of repetition_penalty is not valid."
     assert -2.0 <= args.presence_penalty <= 2.0, "Value of presence_penalty is not valid."
     assert -2.0 <= args.frequency_penalty <= 2.0, "Value of frequency_penalty is not valid."
+    logit_bias = json.loads(args.logit_bias) if args.logit_bias else {}
+    assert isinstance(logit_bias, dict), "Value of logit_bias should be a JSON object."
+    logit_bias = {int(k): float(v) for k, v in logit_bias.items()}  # JSON object keys are strings
+    assert 0 <= args.min_tokens <= args.max_new_tokens, "Value of min_tokens is not valid."
 
     from llmss_amd.engine import LLMEngine, SamplingParams, build_model
     from llmss_amd.parallel.dist import initialize_distributed
@@ -150,7 +175,9 @@ def main(argv=None):
     params = SamplingParams(max_new_tokens=args.max_new_tokens, is_greedy=args.is_greedy,
                             temperature=args.temperature, top_p=args.top_p, top_k=args.top_k, seed=seed,
                             logprobs=args.logprobs, repetition_penalty=args.repetition_penalty,
-                            presence_penalty=args.presence_penalty, frequency_penalty=args.frequency_penalty)
+                            presence_penalty=args.presence_penalty, frequency_penalty=args.frequency_penalty,
+                            logit_bias=logit_bias, banned_token_ids=args.banned_token_ids,
+                            allowed_token_ids=args.allowed_token_ids, min_tokens=args.min_tokens).validate()
     eos = getattr(tokenizer, "eos_token_id", None)
     prompts = [encode(tokenizer, p) for p in args.prompts]
     max_len = model.cfg.max_position_embeddings
@@ -161,7 +188,8 @@ def main(argv=None):
         engine = LLMEngine(model, max_num_seqs=max(1, len(prompts)), eos_token_id=eos,
                            # --logprobs 0 still needs the kernel, hence an engine with N >= 1
                            max_logprobs=0 if args.logprobs is None else max(1, args.logprobs),
-                           penalties=params.has_penalties)  # the state only when a flag differs from its default
+                           # the states only when a flag differs from its default
+                           penalties=params.has_penalties, constraints=params.has_constraints)
         per = [SamplingParams(**{**params.__dict__, "seed": seed + i}) for i in range(len(prompts))]
         if args.logprobs is None:
             outputs = engine.generate(prompts, per)

@@ -47,6 +47,10 @@ void launch_apply_penalties(const void* logits, int64_t ld, void* out, int64_t l
                             const void* new_tokens, const void* rep, const void* pres, const void* freq, hipStream_t st);
 void launch_penalty_reset(void* state, int64_t lds, int nslots, int width, const void* slots, int R, const void* cu,
                           int ntok, const void* tokens, const void* words, hipStream_t st);
+void launch_apply_token_edits(const void* logits, int64_t ld, void* out, int64_t ldo, bool fp32, int B, int W, int lo,
+                              int vocab, const void* edit_ids, int64_t ld_ids, const void* edit_vals,
+                              int64_t ld_vals, const void* edit_meta, int64_t ld_meta, int nslots, int E,
+                              const void* slots, const void* nout, hipStream_t st);
 void launch_attn_extend(const void* q, int64_t q_stride, const void* k_cache, const void* v_cache,
                         const void* block_tables, int max_blocks, const void* cu_q, const void* ctx_lens, void* out,
                         int64_t out_stride, int B, int max_qlen, int nh, int nkv, int D, int bs, float scale,
@@ -155,6 +159,13 @@ PYBIND11_MODULE(_C, m) {
   m.def("penalty_reset", [](uintptr_t state, int64_t lds, int nslots, int width, uintptr_t slots, int R, uintptr_t cu,
                             int ntok, uintptr_t tokens, uintptr_t words, uintptr_t st) {
     launch_penalty_reset(P(state), lds, nslots, width, CP(slots), R, CP(cu), ntok, CP(tokens), CP(words), S(st));
+  });
+  m.def("apply_token_edits", [](uintptr_t lg, int64_t ld, uintptr_t out, int64_t ldo, bool fp32, int B, int W, int lo,
+                                int vocab, uintptr_t ids, int64_t ld_ids, uintptr_t vals, int64_t ld_vals,
+                                uintptr_t meta, int64_t ld_meta, int nslots, int E, uintptr_t slots, uintptr_t nout,
+                                uintptr_t st) {
+    launch_apply_token_edits(CP(lg), ld, P(out), ldo, fp32, B, W, lo, vocab, CP(ids), ld_ids, CP(vals), ld_vals,
+                             CP(meta), ld_meta, nslots, E, CP(slots), CP(nout), S(st));
   });
   m.def("attn_extend", [](uintptr_t q, int64_t qs, uintptr_t kc, uintptr_t vc, uintptr_t bt, int maxb, uintptr_t cu,
                           uintptr_t cl, uintptr_t out, int64_t os, int B, int maxq, int nh, int nkv, int D, int bs,

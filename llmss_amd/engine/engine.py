@@ -35,7 +35,7 @@ from ..ops import hip as _hip_ops
 from ..utils.logging import get_logger
 from ..utils.tracing import PhaseTimer
 from ..utils.tracing import range as trace_range
-from .sampling import MAX_TOP_LOGPROBS, SamplingParams, step_seeds
+from .sampling import MAX_TOKEN_EDITS, MAX_TOP_LOGPROBS, SamplingParams, resolve_token_edits, step_seeds
 
 log = get_logger(__name__)
 
@@ -61,6 +61,8 @@ class Request:
     # params.logprobs most likely (token id, log-probability) pairs at its position
     output_logprobs: List[float] = field(default_factory=list)
     output_top_logprobs: List[List[Tuple[int, float]]] = field(default_factory=list)
+    # params.has_constraints: resolve_token_edits' (early list, late list, fill), made once at admission
+    edits: Optional[tuple] = None
 
     @property
     def all_ids(self) -> List[int]:
@@ -96,15 +98,19 @@ class _DecodeBuffers:
     fp32 (the sampled token's, then the top N) and ``lp_i`` [max_b, N] int32 (their ids) with two pinned host sets.
     ``penalties`` appends ``pslot`` (i32, after the block tables) and ``rep`` / ``pres`` / ``freq`` (f32, after top_p) to
     the staging blob - without it every offset is as before - and keeps the penalised logits, one static buffer per
-    logits width (``pen_out``)."""
+    logits width (``pen_out``). ``constraints`` appends ``cslot`` and ``cnout`` (i32, after ``pslot`` when both are on)
+    and keeps the constrained logits the same way (``con_out``)."""
 
-    def __init__(self, max_b: int, max_blocks: int, device, max_logprobs: int = 0, penalties: bool = False):
+    def __init__(self, max_b: int, max_blocks: int, device, max_logprobs: int = 0, penalties: bool = False,
+                 constraints: bool = False):
         B, MB = max_b, max_blocks
         self.max_b, self.max_blocks = B, MB
         self.penalties = bool(penalties)
+        self.constraints = bool(constraints)
         pin = torch.cuda.is_available() and device.type == "cuda"
-        self.o32 = 4 * B * 8  # ids|pos|slots|seeds (i64) | ctx|topk|bt[|pslot] (i32) | temp|topp[|rep|pres|freq] (f32)
-        self.of32 = self.o32 + (2 * B + B * MB + (B if penalties else 0)) * 4
+        # ids|pos|slots|seeds (i64) | ctx|topk|bt[|pslot][|cslot|cnout] (i32) | temp|topp[|rep|pres|freq] (f32)
+        self.o32 = 4 * B * 8
+        self.of32 = self.o32 + (2 * B + B * MB + (B if penalties else 0) + (2 * B if constraints else 0)) * 4
         nbytes = self.of32 + (5 if penalties else 2) * B * 4
         self.h = [torch.zeros(nbytes, dtype=torch.uint8, pin_memory=pin) for _ in range(2)]
         self.d = torch.zeros(nbytes, dtype=torch.uint8, device=device)
@@ -118,9 +124,14 @@ class _DecodeBuffers:
         self.bt = self.d_i32[2 * B:2 * B + B * MB].view(B, max_blocks)
         self.temp, self.topp = self.d_f32[:B], self.d_f32[B:2 * B]
         if penalties:
-            self.pslot = self.d_i32[2 * B + B * MB:]
+            self.pslot = self.d_i32[2 * B + B * MB:3 * B + B * MB]
             self.rep, self.pres, self.freq = (self.d_f32[i * B:(i + 1) * B] for i in (2, 3, 4))
             self._pen_out = {}
+        if constraints:
+            self.o_con = 2 * B + B * MB + (B if penalties else 0)  # int32 words before cslot
+            self.cslot = self.d_i32[self.o_con:self.o_con + B]
+            self.cnout = self.d_i32[self.o_con + B:self.o_con + 2 * B]
+            self._con_out = {}
         N = self.max_logprobs = max_logprobs
         if N > 0:
             self.lp_f = torch.zeros(max_b, 1 + N, dtype=torch.float32, device=device)
@@ -142,10 +153,19 @@ class _DecodeBuffers:
             self._pen_out[key] = torch.zeros(self.max_b, like.shape[1], dtype=like.dtype, device=like.device)
         return self._pen_out[key][:b]
 
-    def fill(self, k, b_pad, ids, pos, slots, seeds, ctx, topk, bt, temp, topp, pen=None):
+    def con_out(self, b: int, like: torch.Tensor) -> torch.Tensor:
+        """The static buffer the constrained copy of the [b, width] logits ``like`` goes to (as ``pen_out``, and
+        apart from it: the penalised logits are the constraint launch's input)."""
+        key = (like.shape[1], like.dtype)
+        if key not in self._con_out:
+            self._con_out[key] = torch.zeros(self.max_b, like.shape[1], dtype=like.dtype, device=like.device)
+        return self._con_out[key][:b]
+
+    def fill(self, k, b_pad, ids, pos, slots, seeds, ctx, topk, bt, temp, topp, pen=None, con=None):
         """Stage one step's inputs in set k and copy them to the device. ``ids=None``: the input ids
         are the previous step's sampled tokens, copied on the device (same rows). ``pen``: the rows' (penalty slot,
-        repetition, presence, frequency) arrays; padded rows get slot -1."""
+        repetition, presence, frequency) arrays; padded rows get slot -1. ``con``: the rows' (constraint slot, tokens
+        generated so far) arrays; padded rows get slot -1."""
         n = len(pos)
         B, MB = self.max_b, self.max_blocks
         h = self.h[k]
@@ -168,12 +188,19 @@ class _DecodeBuffers:
         hf[B:B + n] = topp
         hf[B + n:B + b_pad] = 1
         if self.penalties:
-            ps = hi32[2 * B + B * MB:]
+            ps = hi32[2 * B + B * MB:3 * B + B * MB]
             ps[:b_pad] = -1
             if pen is not None:
                 ps[:n] = pen[0]
                 for j, arr in enumerate(pen[1:], start=2):
                     hf[j * B:j * B + n] = arr
+        if self.constraints:
+            cs = hi32[self.o_con:self.o_con + 2 * B]
+            cs[:b_pad] = -1
+            cs[B:B + b_pad] = 0
+            if con is not None:
+                cs[:n] = con[0]
+                cs[B:B + n] = con[1]
         self.d.copy_(h, non_blocking=True)
         if ids is None:
             self.ids[:n].copy_(self.out[:n])
@@ -185,8 +212,14 @@ class LLMEngine:
                  kv_fraction: float = 0.9, use_graphs: Optional[bool] = None, eos_token_id: Optional[int] = None,
                  graph_buckets: Optional[Sequence[int]] = None, check_tokens: Optional[bool] = None,
                  autotune: Optional[bool] = None, prefill_chunk: Optional[int] = None,
-                 kv_dtype: Optional[str] = None, max_logprobs: int = 0, penalties: bool = False):
+                 kv_dtype: Optional[str] = None, max_logprobs: int = 0, penalties: bool = False,
+                 constraints: bool = False):
         self.model = model
+        # launch-time opt-in: True keeps every running sequence's resolved token constraints (logit_bias, banned /
+        # allowed tokens, min_tokens: two lists of at most MAX_TOKEN_EDITS (token, value) pairs) on the device and runs
+        # the constraint launch between the penalties and the sampler; False leaves graphs, buffers and steps as they
+        # are and rejects requests that ask for a constraint
+        self.constraints = bool(constraints)
         # launch-time opt-in: True keeps every running sequence's token history on the device (one int32 word per
         # slot and token) and runs the penalty launch between the LM head and the sampler; False leaves graphs,
         # buffers and steps as they are and rejects requests that ask for a penalty
@@ -222,6 +255,19 @@ class LLMEngine:
             if model.dtype not in (torch.bfloat16, torch.float32):
                 raise ValueError(f"penalties need bfloat16 or float32 logits, the model computes {model.dtype}")
             self.pen_state = torch.zeros(max_num_seqs, self.cfg.vocab_size, dtype=torch.int32, device=self.device)
+        # constraint state, likewise: one block per slot - early and late ids, early and late values, meta - so that
+        # one host-to-device copy writes a slot whole; edit_ids / edit_vals / edit_meta are views of it
+        self.con_state = None
+        self._con_free: List[int] = list(range(max_num_seqs - 1, -1, -1))
+        self._con_slot: Dict[int, int] = {}  # request id -> constraint slot; holders are always running sequences
+        if self.constraints:
+            if model.dtype not in (torch.bfloat16, torch.float32):
+                raise ValueError(f"constraints need bfloat16 or float32 logits, the model computes {model.dtype}")
+            E = MAX_TOKEN_EDITS
+            self.con_state = torch.zeros(max_num_seqs, 4 * E + 4, dtype=torch.int32, device=self.device)
+            self.edit_ids = self.con_state[:, :2 * E].view(max_num_seqs, 2, E)
+            self.edit_vals = self.con_state[:, 2 * E:4 * E].view(torch.float32).view(max_num_seqs, 2, E)
+            self.edit_meta = self.con_state[:, 4 * E:]
         self.num_blocks = self.tp.all_reduce_int(num_blocks or self._auto_blocks(kv_fraction), "min")
         self.kv = model.allocate_kv_cache(self.num_blocks, block_size)
         # chunked prefill: prompts are cut to fit the per-step token budget and ride along with the
@@ -248,6 +294,8 @@ class LLMEngine:
                       "preemptions": 0, "decode_time_s": 0.0, "prefill_time_s": 0.0, "peak_live_kv_blocks": 0}
         if self.penalties:
             self.stats["penalty_state_bytes"] = self.pen_state.numel() * 4
+        if self.constraints:
+            self.stats["constraint_state_bytes"] = self.con_state.numel() * 4
         self.timer = PhaseTimer()  # LLMSS_TIMING=1: HIP-event device time per phase; LLMSS_ROCTX=1: roctx ranges
         self._host_prof = self.timer.enabled  # LLMSS_TIMING=1 also records host-side time per engine phase
         self.use_graphs = self.is_gpu if use_graphs is None else (use_graphs and self.is_gpu)
@@ -273,8 +321,8 @@ class LLMEngine:
         # (column-chunked all-reduces beside the next chunk's GEMM)
         self.decode_schedule: Dict[int, str] = {}
         self.tp.check_consistent("LLMEngine", self.fingerprint())
-        self.buf = _DecodeBuffers(self.buckets[-1], self.max_blocks, self.device, self.max_logprobs, self.penalties) \
-            if self.is_gpu else None
+        self.buf = _DecodeBuffers(self.buckets[-1], self.max_blocks, self.device, self.max_logprobs, self.penalties,
+                                  self.constraints) if self.is_gpu else None
         if self.is_gpu:
             _hip_ops.reserve_workspace(self.device, 64 << 20)
             for b in self.decode_batch_sizes():
@@ -381,7 +429,7 @@ class LLMEngine:
                 "buckets": list(self.buckets), "graphs": bool(self.use_graphs),
                 "async_decode": self.async_decode, "eos": self.eos, "prefill_chunk": self.prefill_chunk, "window": self.window,
                 "dist_sampling": self.dist_sampling, "max_logprobs": self.max_logprobs, "kv_fp8": bool(self.model.kv_fp8),
-                "penalties": self.penalties,
+                "penalties": self.penalties, "constraints": self.constraints,
                 "overlap_rows": self.model.overlap_rows, "bucket_bytes": self.model.bucket_bytes,
                 "tbo_min": self.model.tbo_min, "graph_keys": sorted(self.graphs),
                 "decode_schedule": sorted(self.decode_schedule.items()), "rsag_mode": self.model.rsag_mode,
@@ -539,6 +587,13 @@ class LLMEngine:
             if not self.penalties:
                 raise ValueError("a repetition, presence or frequency penalty was requested but the engine was "
                                  "launched without them (LLMEngine(penalties=True), server --penalties)")
+        edits = None
+        if params.has_constraints:
+            params.validate()
+            if not self.constraints:
+                raise ValueError("logit_bias, banned_token_ids, allowed_token_ids or min_tokens was requested but the "
+                                 "engine was launched without them (LLMEngine(constraints=True), server --constraints)")
+            edits = resolve_token_edits(params, self.eos, self.cfg.vocab_size)  # range, capacity, empty set
         prompt = list(int(t) for t in prompt_ids)
         if not prompt:
             raise ValueError("empty prompt")
@@ -549,7 +604,7 @@ class LLMEngine:
             params = SamplingParams(**{**params.__dict__, "max_new_tokens": max_new})
         rid = self._next_id if req_id is None else int(req_id)
         self._next_id = max(self._next_id, rid + 1)
-        req = Request(rid, prompt, params, params.resolved_seed(), t_arrival=time.perf_counter())
+        req = Request(rid, prompt, params, params.resolved_seed(), t_arrival=time.perf_counter(), edits=edits)
         # the scheduler validates first (a sequence larger than the whole KV pool, a whole prompt over the token
         # budget -> ValueError): a rejected request is never registered, so nothing is left behind
         self.sched.add(rid, len(prompt), max_new)
@@ -562,6 +617,7 @@ class LLMEngine:
             r = self.requests[rid]
             r.finished, r.finish_reason = True, "abort"
             self._pen_release(rid)
+            self._con_release(rid)
             if self._pending:  # rows of in-flight decode steps: no speculative successor may touch it
                 self._aborted.add(rid)
 
@@ -628,6 +684,56 @@ class LLMEngine:
         new = np.where(fresh, -1, np.array([r.last_id for r in reqs], dtype=np.int64))
         return tuple(torch.from_numpy(a).to(self.device) for a in (slot, new, rep, pres, freq)) + (None,)
 
+    # -------------------------------------------------------------------------- token constraints
+    def _con_release(self, rid: int):
+        """Give a request's constraint slot back (finish, abort, preemption). A decode step still in flight may go on
+        reading it: the next holder's copy overwrites it later on the same stream."""
+        s = self._con_slot.pop(rid, None)
+        if s is not None:
+            self._con_free.append(s)
+
+    def _con_acquire(self, reqs: List[Request]) -> bool:
+        """Give every request of a sampling step that has constraints and holds no slot the lowest free one, its
+        lists and meta written ahead of the step's launch - one host-to-device copy on the compute stream per run of
+        neighbouring slots, so one copy when the step's new slots lie side by side: the step completes its known
+        tokens for the first time - the last chunk of its prompt, or of the re-prefill after a preemption. The slot
+        then stays as it is until it is released (which list applies is the launch's ``nout`` against min_tokens).
+        Returns whether any slot was taken."""
+        rows = {}
+        E = MAX_TOKEN_EDITS
+        for r in reqs:
+            if r.edits is None or r.id in self._con_slot:
+                continue
+            self._con_free.sort(reverse=True)
+            s = self._con_slot[r.id] = self._con_free.pop()
+            early, late, fill = r.edits
+            ids, vals, meta = ops.pack_token_edits(early, late, fill, r.params.min_tokens, E)
+            rows[s] = np.concatenate([ids.reshape(-1), vals.reshape(-1).view(np.int32), meta])
+        order = sorted(rows)
+        i = 0
+        while i < len(order):
+            j = i + 1
+            while j < len(order) and order[j] == order[j - 1] + 1:
+                j += 1
+            self.con_state[order[i]:order[j - 1] + 1].copy_(torch.from_numpy(np.stack([rows[s] for s in order[i:j]])))
+            i = j
+        return bool(rows)
+
+    def _con_slots(self, reqs: List[Request]) -> np.ndarray:
+        return np.array([self._con_slot.get(r.id, -1) for r in reqs], dtype=np.int32)
+
+    def _con_eager(self, reqs: List[Request]):
+        """Constraint inputs of an eager sampling step over ``reqs`` (_forward_sample's ``con``), or None when no row
+        holds a slot (the launch would be a copy)."""
+        if not self.constraints:
+            return None
+        self._con_acquire(reqs)
+        slot = self._con_slots(reqs)
+        if not (slot >= 0).any():
+            return None
+        nout = np.array([len(r.output_ids) for r in reqs], dtype=np.int32)
+        return torch.from_numpy(slot).to(self.device), torch.from_numpy(nout).to(self.device), None
+
     # -------------------------------------------------------------------------- step
     def _sampling_arrays(self, reqs: List[Request]):
         temp = np.array([r.params.k_temperature for r in reqs], dtype=np.float32)
@@ -676,6 +782,7 @@ class LLMEngine:
                                f"{self.sched.num_running()} running sequences")
         for rid in batch.preempted.tolist():  # recomputed later: the re-prefill takes a state row again
             self._pen_release(int(rid))
+            self._con_release(int(rid))
         if batch.kind != 0:
             self.stats["preemptions"] += len(batch.preempted)
             ids = batch.ids
@@ -744,6 +851,7 @@ class LLMEngine:
                 continue
             fins[i] = True
             self._pen_release(r.id)
+            self._con_release(r.id)
         self.sched.on_tokens(ids, fins)
         self._last_fins = fins
         self.stats["steps"] += 1
@@ -797,7 +905,8 @@ class LLMEngine:
             return []
         temp, topk, topp, seeds = self._sampling_arrays(reqs)
         tok = self._forward_sample(inp, *(torch.from_numpy(a).to(dev) for a in (temp, topk, topp, seeds)),
-                                   dist=self._dist_ok(temp, topk), pen=self._pen_eager(reqs))
+                                   dist=self._dist_ok(temp, topk), pen=self._pen_eager(reqs),
+                                   con=self._con_eager(reqs))
         self._step_lps = self._lps_to_host()
         return tok.cpu().tolist()
 
@@ -812,12 +921,21 @@ class LLMEngine:
         out = buf.pen_out(logits.shape[0], logits) if buf is not None else None
         return ops.apply_penalties(logits, self.pen_state, slots, new, rep, pres, freq, lo, vocab, out)
 
-    def _forward_sample(self, inp: StepInput, temp, topk, topp, seeds, out=None, dist=False, lp_out=None, pen=None):
+    def _constrain(self, logits, con, lo, vocab):
+        """The constraint launch between the penalties and the sampler: ``con`` = (slots, tokens generated so far,
+        static decode buffers or None). Out of place - the raw logits stay for the log-probabilities."""
+        slots, nout, buf = con
+        out = buf.con_out(logits.shape[0], logits) if buf is not None else None
+        return ops.apply_token_edits(logits, self.edit_ids, self.edit_vals, self.edit_meta, slots, nout, lo, vocab, out)
+
+    def _forward_sample(self, inp: StepInput, temp, topk, topp, seeds, out=None, dist=False, lp_out=None, pen=None,
+                        con=None):
         """Forward + LM head + sampler. ``dist``: each rank keeps its logit shard and only candidates
         are gathered (ops.sample_distributed); otherwise the [B, V] logits are all-gathered. With max_logprobs > 0
         a separate launch after the sampler reads the same logits and the sampled ids (ops.token_logprobs; on the
         ``dist`` path per-shard packs, an all-gather and a combine) into ``lp_out`` or ``self._lps``. ``pen``: the
-        sampler reads the penalised copy of the logits (_penalise); the log-probabilities stay those of the raw ones."""
+        sampler reads the penalised copy of the logits (_penalise); ``con``: then the constrained copy of those
+        (_constrain); the log-probabilities stay those of the raw ones."""
         m = self.model
         V = self.cfg.vocab_size
         N = self.max_logprobs
@@ -827,6 +945,8 @@ class LLMEngine:
                 h = h.index_select(0, inp.last_idx)
             local = m.local_logits(h)
             plocal = local if pen is None else self._penalise(local, pen, m.vocab_lo, V)
+            if con is not None:
+                plocal = self._constrain(plocal, con, m.vocab_lo, V)
             tok = ops.sample_distributed(plocal, self.tp, m.vocab_lo, V, temp, topk, topp, seeds, out=out)
             if N > 0:
                 self._lps = ops.token_logprobs_distributed(local, self.tp, m.vocab_lo, V, tok, N, out=lp_out)
@@ -834,6 +954,8 @@ class LLMEngine:
         logits = m(inp, self.kv)
         vocab = min(V, logits.shape[-1])
         plogits = logits if pen is None else self._penalise(logits, pen, 0, vocab)
+        if con is not None:
+            plogits = self._constrain(plogits, con, 0, vocab)
         if logits.is_cuda:
             tok = _hip_ops.sample(plogits, temp, topk, topp, seeds, vocab=vocab, out=out)
         else:
@@ -856,8 +978,9 @@ class LLMEngine:
         # every decode step registers its input token before the penalties are applied
         pen = (buf.pslot[:b], buf.ids[:b] if pnew is None else pnew, buf.rep[:b], buf.pres[:b], buf.freq[:b], buf) \
             if self.penalties else None
+        con = (buf.cslot[:b], buf.cnout[:b], buf) if self.constraints else None
         self._forward_sample(inp, buf.temp[:b], buf.topk[:b], buf.topp[:b], buf.seeds[:b], out=buf.out[:b],
-                             dist=dist, lp_out=buf.lp_out(b), pen=pen)
+                             dist=dist, lp_out=buf.lp_out(b), pen=pen, con=con)
 
     def _decode_cpu(self, batch, reqs: List[Request]) -> List[int]:
         ids = np.array([r.last_id for r in reqs], dtype=np.int64)
@@ -868,7 +991,7 @@ class LLMEngine:
                         ctx_lens=torch.from_numpy(batch.ctx_lens.astype(np.int32)), max_ctx=self.max_model_len,
                         window=self.window)
         tok = self._forward_sample(inp, temp, topk, topp, seeds, dist=self._dist_ok(temp, topk),
-                                   pen=self._pen_eager(reqs))
+                                   pen=self._pen_eager(reqs), con=self._con_eager(reqs))
         self._step_lps = self._lps_to_host()
         return tok.tolist()
 
@@ -878,9 +1001,13 @@ class LLMEngine:
         collected step when the running set is unchanged (every member then got one token)."""
         last = self._last_rec
         fresh = self._pen_acquire(reqs) if self.penalties else None
+        # a constraint slot taken here (the scheduler hands a last prompt chunk of one token out as a decode row) is
+        # written before the launch and changes no other input of the step: the step still replays its graph
+        took = self._con_acquire(reqs) if self.constraints else False
         if last is not None and last["ids"].shape == ids.shape and np.array_equal(last["ids"], ids) \
-                and last["keep"].all() and not (fresh is not None and fresh.any()):
-            c = {k: last[k] for k in ("temp", "topk", "topp", "seed", "maxnew") + (("pen",) if self.penalties else ())}
+                and last["keep"].all() and not (fresh is not None and fresh.any()) and not took:
+            c = {k: last[k] for k in ("temp", "topk", "topp", "seed", "maxnew") + (("pen",) if self.penalties else ())
+                 + (("con",) if self.constraints else ())}
             c["nout"] = last["nout"] + 1
             c["last"] = last["tokens"]
         else:
@@ -895,6 +1022,8 @@ class LLMEngine:
                 c["pen"] = self._pen_arrays(reqs)
                 if fresh.any():  # rows whose reset covers their input token: this step registers nothing for them
                     c["pnew"] = np.where(fresh, -1, c["last"])
+            if self.constraints:
+                c["con"] = self._con_slots(reqs)
         c.update(ids=ids, reqs=reqs, n=len(reqs), pos=batch.positions, ctx=batch.ctx_lens.astype(np.int32),
                  slots=batch.slots, bt=batch.block_table, keep=np.ones(len(reqs), dtype=bool))
         c["dist"] = self._dist_ok(c["temp"], c["topk"])
@@ -910,7 +1039,8 @@ class LLMEngine:
         with self.timer.phase("decode"):
             buf.fill(k, b, None if device_ids else rec.pop("last"), rec["pos"], rec["slots"],
                      step_seeds(rec["seed"], rec["nout"]), rec["ctx"], rec["topk"], rec["bt"], rec["temp"],
-                     rec["topp"], pen=rec.get("pen"))
+                     rec["topp"], pen=rec.get("pen"),
+                     con=(rec["con"], rec["nout"]) if self.constraints else None)
             key = (b, bool(rec["dist"]))
             if self._host_prof:
                 # was the GPU already idle (every earlier step done) when this step was launched?
@@ -974,6 +1104,8 @@ class LLMEngine:
             rec["topk"] = np.where(alive, cur["topk"], 1).astype(np.int32)
         if self.penalties:  # dead rows hold no slot: their row of the state may already be another sequence's
             rec["pen"] = (np.where(alive, cur["pen"][0], -1).astype(np.int32),) + tuple(cur["pen"][1:])
+        if self.constraints:  # likewise
+            rec["con"] = np.where(alive, cur["con"], -1).astype(np.int32)
         self._launch_decode(rec, device_ids=True)
 
     def _collect_decode(self):
@@ -1035,6 +1167,8 @@ class LLMEngine:
         buf.d_f32.zero_()
         if self.penalties:
             buf.pslot.fill_(-1)  # padded rows hold no penalty slot: the launch copies them
+        if self.constraints:
+            buf.cslot.fill_(-1)  # nor a constraint slot
         modes = self._decode_modes()
         # warm-up passes (lazy allocations, first launches). Native RCCL: with real collectives, so each
         # algorithm's lazy peer connection happens here and not inside the capture. torch's RCCL process

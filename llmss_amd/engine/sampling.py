@@ -20,17 +20,22 @@ import math
 import numbers
 import os
 from dataclasses import dataclass, field
-from typing import List, Optional
+from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 
 _seed_counter = itertools.count(int.from_bytes(os.urandom(4), "little"))
 MASK64 = (1 << 64) - 1
 MAX_TOP_LOGPROBS = 20  # most alternatives per generated position a request may ask for (csrc/logprobs.hip)
+MAX_TOKEN_EDITS = 512  # most listed tokens of a request's early or late constraint list (csrc/constraints.hip)
 
 
 def _is_number(v) -> bool:
     return isinstance(v, numbers.Real) and not isinstance(v, bool)
+
+
+def _is_int(v) -> bool:
+    return isinstance(v, numbers.Integral) and not isinstance(v, bool)
 
 
 @dataclass
@@ -55,10 +60,23 @@ class SamplingParams:
     repetition_penalty: float = 1.0
     presence_penalty: float = 0.0
     frequency_penalty: float = 0.0
+    # token constraints, a sparse edit of the logits row after the penalties and before temperature, top-k and top-p
+    # (csrc/constraints.hip; resolve_token_edits below is the definition). logit_bias adds a value in [-100, 100] to a
+    # token's logit; a banned token's logit becomes -inf; a non-empty allowed_token_ids makes every other token's
+    # -inf; while a sequence has generated fewer than min_tokens tokens, EOS (unless ignore_eos) and the
+    # stop_token_ids are -inf. Anything but the defaults needs an engine launched with constraints=True.
+    logit_bias: Dict[int, float] = field(default_factory=dict)
+    banned_token_ids: List[int] = field(default_factory=list)
+    allowed_token_ids: List[int] = field(default_factory=list)
+    min_tokens: int = 0
 
     @property
     def has_penalties(self) -> bool:
         return not (self.repetition_penalty == 1.0 and self.presence_penalty == 0.0 and self.frequency_penalty == 0.0)
+
+    @property
+    def has_constraints(self) -> bool:
+        return bool(self.logit_bias or self.banned_token_ids or self.allowed_token_ids or self.min_tokens != 0)
 
     def validate(self) -> "SamplingParams":
         """Reference validation (generate.py:37-40)."""
@@ -80,6 +98,19 @@ class SamplingParams:
             v = getattr(self, name)
             if not (_is_number(v) and math.isfinite(v) and -2.0 <= v <= 2.0):
                 raise ValueError(f"Value of {name} should be a finite number in [-2, 2].")
+        if not isinstance(self.logit_bias, dict):
+            raise ValueError("Value of logit_bias should be a dict of token id -> bias.")
+        for name, ids in (("logit_bias", list(self.logit_bias)), ("banned_token_ids", self.banned_token_ids),
+                          ("allowed_token_ids", self.allowed_token_ids)):
+            if not isinstance(ids, (list, tuple)) or not all(_is_int(t) and t >= 0 for t in ids):
+                raise ValueError(f"Token ids of {name} should be integers >= 0.")
+            if len(set(ids)) != len(ids):
+                raise ValueError(f"Token ids of {name} should be distinct.")
+        for v in self.logit_bias.values():
+            if not (_is_number(v) and math.isfinite(v) and -100.0 <= v <= 100.0):
+                raise ValueError("Values of logit_bias should be finite numbers in [-100, 100].")
+        if not (_is_int(self.min_tokens) and 0 <= self.min_tokens <= self.max_new_tokens):
+            raise ValueError("Value of min_tokens should be an integer in 0..max_new_tokens.")
         return self
 
     def resolved_seed(self) -> int:
@@ -99,6 +130,48 @@ class SamplingParams:
     @property
     def k_top_p(self) -> float:
         return float(self.top_p)
+
+
+def resolve_token_edits(params: SamplingParams, eos: Optional[int], vocab: int
+                        ) -> Tuple[List[Tuple[int, float]], List[Tuple[int, float]], bool]:
+    """A request's token constraints as (early list, late list, fill): two lists of distinct (token, value) pairs in
+    ascending token order, value -inf (forbidden) or a finite bias added to the logit; ``fill``: every token that is
+    not listed is forbidden too. The late list is in force once the sequence has generated min_tokens tokens, the
+    early one before that (empty and unused when min_tokens == 0).
+
+    late, with a non-empty allowed_token_ids: fill, and every allowed token that is not banned with its bias (0.0
+    without one); otherwise no fill, and every token of logit_bias or banned_token_ids: -inf if banned, else its bias.
+    early: the late list with the stop set S = {eos unless ignore_eos or eos is None} | stop_token_ids forced out -
+    removed from a filled list, added or overwritten with -inf otherwise.
+
+    ValueError: a token id at or past ``vocab``, a filled list that leaves no token, more than MAX_TOKEN_EDITS entries."""
+    bias, banned, allowed = params.logit_bias, set(params.banned_token_ids), params.allowed_token_ids
+    for name, ids in (("logit_bias", bias), ("banned_token_ids", banned), ("allowed_token_ids", allowed)):
+        bad = [t for t in ids if not 0 <= t < vocab]
+        if bad:
+            raise ValueError(f"{name}: token ids {sorted(bad)[:8]} are outside the vocabulary of {vocab}")
+    fill = len(allowed) > 0
+    if fill:
+        late = {int(v): float(bias.get(v, 0.0)) for v in allowed if v not in banned}
+    else:
+        late = {int(v): float("-inf") if v in banned else float(bias[v]) for v in set(bias) | banned}
+    early = {}
+    if params.min_tokens > 0:
+        stop = {int(t) for t in params.stop_token_ids}
+        if eos is not None and not params.ignore_eos:
+            stop.add(int(eos))
+        if fill:
+            early = {v: a for v, a in late.items() if v not in stop}
+        else:
+            early = {**late, **{t: float("-inf") for t in stop if 0 <= t < vocab}}
+    for name, lst, used in (("early", early, params.min_tokens > 0), ("late", late, True)):
+        if used and fill and not lst:
+            raise ValueError(f"the token constraints leave no token to sample "
+                             f"{'before min_tokens' if name == 'early' else 'at all'}")
+        if len(lst) > MAX_TOKEN_EDITS:
+            raise ValueError(f"the token constraints list {len(lst)} tokens ({name}), more than MAX_TOKEN_EDITS = "
+                             f"{MAX_TOKEN_EDITS}")
+    return sorted(early.items()), sorted(late.items()), fill
 
 
 def step_seed(seed: int, step: int) -> int:

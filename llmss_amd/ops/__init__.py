@@ -14,7 +14,8 @@ from . import reference as ref
 
 __all__ = ["add_norm", "embed", "rope_cache", "attn_prefill", "attn_decode", "attn_extend", "linear", "sample", "quant_fp8_rows",
            "rope_tables", "glu_interleave", "glu_split", "cross_entropy", "token_logprobs",
-           "token_logprobs_distributed", "MAX_TOP_LOGPROBS", "apply_penalties", "penalty_reset", "penalty_words"]
+           "token_logprobs_distributed", "MAX_TOP_LOGPROBS", "apply_penalties", "penalty_reset", "penalty_words",
+           "apply_token_edits", "pack_token_edits"]
 
 rope_tables = ref.rope_tables
 glu_interleave = ref.glu_interleave
@@ -207,6 +208,17 @@ def penalty_reset(state, slots, cu, tokens, words):
     if state.is_cuda:
         return _hip().penalty_reset(state, slots, cu, tokens, words)
     return ref.penalty_reset(state, slots, cu, tokens, words)
+
+
+pack_token_edits = ref.pack_token_edits
+
+
+def apply_token_edits(logits, edit_ids, edit_vals, edit_meta, slots, nout, lo=0, vocab=None, out=None):
+    """Token constraints (logit_bias, banned / allowed tokens, min_tokens) as a sparse per-row edit of the logits, out
+    of place (ops/reference.py apply_token_edits is the definition, csrc/constraints.hip the GPU kernel)."""
+    if logits.is_cuda:
+        return _hip().apply_token_edits(logits, edit_ids, edit_vals, edit_meta, slots, nout, lo, vocab, out)
+    return ref.apply_token_edits(logits, edit_ids, edit_vals, edit_meta, slots, nout, lo, vocab, out)
 
 
 def quant_fp8_rows(w):

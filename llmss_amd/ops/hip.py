@@ -995,3 +995,53 @@ def penalty_reset(state, slots, cu, tokens, words):
     lib().penalty_reset(state.data_ptr(), state.stride(0), state.shape[0], state.shape[1], slots.data_ptr(), R,
                         cu.data_ptr(), n, tokens.data_ptr(), words.data_ptr(), _stream())
     return state
+
+
+# ---------------------------------------------------------------------------------------- token constraints
+def apply_token_edits(logits, edit_ids, edit_vals, edit_meta, slots, nout, lo=0, vocab=None, out=None):
+    """Token constraints over ``logits`` [B, W] (bf16 / fp32, any row stride) whose column j is global token
+    ``lo + j``, written out of place into ``out`` (csrc/constraints.hip; ops/reference.py apply_token_edits is the
+    definition). ``edit_ids`` [S, 2, E] int32, ``edit_vals`` [S, 2, E] fp32 and ``edit_meta`` [S, 4] int32 are the
+    constraint slots' state, which the launch only reads; ``slots`` [B] int32 (-1: copy the row), ``nout`` [B] int32
+    the tokens each row's sequence has generated so far."""
+    _check(torch.is_tensor(logits) and logits.is_cuda and logits.dim() == 2 and (logits.shape[1] <= 1 or
+                                                                                logits.stride(1) == 1),
+           "logits must be [B, W] GPU rows")
+    dev = logits.device
+    _check(dev.index == torch.cuda.current_device(),
+           f"logits is on {dev} but the current device is cuda:{torch.cuda.current_device()}")
+    _check(logits.dtype in (torch.bfloat16, torch.float32), f"logits must be bfloat16 or float32, got {logits.dtype}")
+    B, W = logits.shape
+    _check(B <= 1 or logits.stride(0) >= W, "logits rows overlap")
+    def slot_rows(t):  # each slot's row contiguous, the slots themselves apart by any stride that keeps them disjoint
+        n = t[0].numel() if t.shape[0] else 0
+        return t.shape[0] == 0 or (t[0].is_contiguous() and (t.shape[0] == 1 or t.stride(0) >= n))
+    _check(torch.is_tensor(edit_ids) and edit_ids.dtype == torch.int32 and edit_ids.dim() == 3
+           and edit_ids.shape[1] == 2 and edit_ids.device == dev and slot_rows(edit_ids),
+           f"edit_ids must be an int32 [S, 2, E] tensor on {dev} with contiguous slots")
+    S, _, E = edit_ids.shape
+    _check(torch.is_tensor(edit_vals) and edit_vals.dtype == torch.float32 and tuple(edit_vals.shape) == (S, 2, E)
+           and edit_vals.device == dev and slot_rows(edit_vals),
+           f"edit_vals must be a float32 [{S}, 2, {E}] tensor on {dev} with contiguous slots")
+    _check(torch.is_tensor(edit_meta) and edit_meta.dtype == torch.int32 and tuple(edit_meta.shape) == (S, 4)
+           and edit_meta.device == dev and slot_rows(edit_meta),
+           f"edit_meta must be an int32 [{S}, 4] tensor on {dev} with contiguous slots")
+    lo = int(lo)
+    vocab = lo + W if vocab is None else int(vocab)
+    _check(lo >= 0 and vocab >= 0, f"need lo >= 0 and vocab >= 0, got lo = {lo}, vocab = {vocab}")
+    _check(B <= 65535 and lo + W < 2 ** 31 and vocab < 2 ** 31, "too many rows or columns")
+    _pen_vec(slots, torch.int32, B, dev, "slots")
+    _pen_vec(nout, torch.int32, B, dev, "nout")
+    if out is None:
+        out = torch.empty(B, W, dtype=logits.dtype, device=dev)
+    _check(torch.is_tensor(out) and out.dtype == logits.dtype and out.device == dev
+           and tuple(out.shape) == (B, W) and (W <= 1 or out.stride(1) == 1),
+           f"out must be a {logits.dtype} [{B}, {W}] tensor with contiguous rows on {dev}")
+    _check(B <= 1 or out.stride(0) >= W, "out rows overlap")
+    _check(not _overlap(out, logits), "out must not alias logits: the raw logits are kept")
+    lib().apply_token_edits(logits.data_ptr(), logits.stride(0), out.data_ptr(), out.stride(0),
+                            logits.dtype == torch.float32, B, W, lo, vocab, edit_ids.data_ptr(),
+                            max(edit_ids.stride(0), 2 * E), edit_vals.data_ptr(), max(edit_vals.stride(0), 2 * E),
+                            edit_meta.data_ptr(), max(edit_meta.stride(0), 4), S, E, slots.data_ptr(),
+                            nout.data_ptr(), _stream())
+    return out

@@ -657,3 +657,52 @@ def penalty_reset(state, slots, cu, tokens, words):
         ok = (t >= 0) & (t < state.shape[1])
         state[s, t[ok]] = words[a:b][ok].to(state.dtype)
     return state
+
+
+# ------------------------------------------------------------------------------------ token constraints
+def pack_token_edits(early, late, fill: bool, min_tokens: int, E: int):
+    """One constraint slot's device rows from ``resolve_token_edits``' lists of (token, value) pairs: ids [2, E] int32
+    and vals [2, E] fp32 (list 0 = early, 1 = late; unused entries id -1, value 0) and meta [4] int32 =
+    (n_early, n_late, fill, min_tokens)."""
+    ids = np.full((2, E), -1, dtype=np.int32)
+    vals = np.zeros((2, E), dtype=np.float32)
+    for k, lst in enumerate((early, late)):
+        if len(lst) > E:
+            raise ValueError(f"{len(lst)} token edits, more than the {E} a slot holds")
+        if lst:
+            ids[k, :len(lst)] = [t for t, _ in lst]
+            vals[k, :len(lst)] = [a for _, a in lst]
+    return ids, vals, np.array([len(early), len(late), int(bool(fill)), int(min_tokens)], dtype=np.int32)
+
+
+def apply_token_edits(logits, edit_ids, edit_vals, edit_meta, slots, nout, lo: int = 0, vocab=None, out=None):
+    """Token constraints (GPU ``apply_token_edits``, csrc/constraints.hip): logit_bias, banned / allowed tokens and
+    min_tokens as a sparse edit of ``logits`` [B, W], whose column j is global token v = lo + j, written out of place.
+    ``edit_ids`` / ``edit_vals`` [S, 2, E] hold each slot's early (0) and late (1) list of distinct tokens with -inf or
+    a finite bias, ``edit_meta`` [S, 4] = (n_early, n_late, fill, min_tokens). Row b with slot ``slots[b]`` >= 0 uses
+    the early list iff ``nout[b]`` < min_tokens. Per column: v >= vocab -> copied; listed with -inf -> -inf; listed
+    with a finite a -> float(x) + a, one fp32 add and one rounding to the logits' dtype; not listed -> -inf if fill,
+    else copied. Rows with slot -1 are copied."""
+    B, W = logits.shape
+    vocab = lo + W if vocab is None else int(vocab)
+    if out is None:
+        out = torch.empty(B, W, dtype=logits.dtype, device=logits.device)
+    out.copy_(logits)
+    n = max(0, min(W, vocab - lo))
+    ninf = float("-inf")
+    for b in range(B):
+        s = int(slots[b])
+        if s < 0 or n == 0:
+            continue
+        n_early, n_late, fill, min_tokens = (int(v) for v in edit_meta[s])
+        k = 0 if int(nout[b]) < min_tokens else 1
+        cnt = n_early if k == 0 else n_late
+        if fill:
+            out[b, :n] = ninf
+        ids = edit_ids[s, k, :cnt].long()
+        vals = edit_vals[s, k, :cnt].float()
+        ok = (ids >= lo) & (ids < lo + n)
+        j, a = ids[ok] - lo, vals[ok]
+        x = logits[b, j].float() + a
+        out[b, j] = torch.where(a == ninf, torch.full_like(x, ninf), x).to(out.dtype)
+    return out

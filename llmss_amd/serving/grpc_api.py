@@ -52,7 +52,8 @@ def _build_pool():
                             ("top_p", FL, 0), ("top_k", I32, 0), ("request_id", S, 0), ("seed", I64, 0),
                             ("prompt_token_ids", I32, 1), ("ignore_eos", B, 0), ("return_logprobs", B, 0),
                             ("top_logprobs", I32, 0), ("repetition_penalty", FL, 0), ("presence_penalty", FL, 0),
-                            ("frequency_penalty", FL, 0)])
+                            ("frequency_penalty", FL, 0), ("logit_bias_ids", I32, 1), ("logit_bias_values", FL, 1),
+                            ("banned_token_ids", I32, 1), ("allowed_token_ids", I32, 1), ("min_tokens", I32, 0)])
     msg("TopLogprobs", [("token_ids", I32, 1), ("logprobs", FL, 1)])
     msg("GenerateResponse", [("prompt", S, 0), ("continuation", S, 0), ("request_id", S, 0), ("token_ids", I32, 1),
                              ("finish_reason", S, 0), ("ttft_s", FL, 0), ("e2e_s", FL, 0), ("token_logprobs", FL, 1),
@@ -102,10 +103,24 @@ def _penalty_fields(req) -> dict:
             "presence_penalty": float(req.presence_penalty), "frequency_penalty": float(req.frequency_penalty)}
 
 
-def _params(req, max_logprobs: Optional[int] = None, penalties: Optional[bool] = None):
+def _constraint_fields(req) -> dict:
+    """The request's token constraints as SamplingParams / protocol.Request fields: logit_bias travels as two parallel
+    repeated fields, whose lengths must agree (ValueError, INVALID_ARGUMENT)."""
+    ids, values = list(req.logit_bias_ids), list(req.logit_bias_values)
+    if len(ids) != len(values):
+        raise ValueError(f"logit_bias_ids has {len(ids)} entries, logit_bias_values {len(values)}")
+    if len(set(ids)) != len(ids):
+        raise ValueError("logit_bias_ids should be distinct")
+    return {"logit_bias": {int(t): float(v) for t, v in zip(ids, values)},
+            "banned_token_ids": [int(t) for t in req.banned_token_ids],
+            "allowed_token_ids": [int(t) for t in req.allowed_token_ids], "min_tokens": int(req.min_tokens)}
+
+
+def _params(req, max_logprobs: Optional[int] = None, penalties: Optional[bool] = None,
+            constraints: Optional[bool] = None):
     """``max_logprobs``: the serving engine's launch-time limit when known - a log-probability request it cannot
-    serve is a ValueError here (INVALID_ARGUMENT), not a failed handle later. ``penalties``: likewise whether the
-    engine was launched with penalties."""
+    serve is a ValueError here (INVALID_ARGUMENT), not a failed handle later. ``penalties``, ``constraints``: likewise
+    whether the engine was launched with penalties / token constraints."""
     from ..engine.sampling import SamplingParams
 
     logprobs = int(req.top_logprobs) if req.return_logprobs else None
@@ -118,11 +133,16 @@ def _params(req, max_logprobs: Optional[int] = None, penalties: Optional[bool] =
     pen = _penalty_fields(req)
     if penalties is False and pen != {"repetition_penalty": 1.0, "presence_penalty": 0.0, "frequency_penalty": 0.0}:
         raise ValueError("penalties are not enabled on this server (--penalties)")
+    con = _constraint_fields(req)
+    if constraints is False and (con["logit_bias"] or con["banned_token_ids"] or con["allowed_token_ids"]
+                                 or con["min_tokens"]):
+        raise ValueError("token constraints are not enabled on this server (--constraints)")
     # proto3 scalars default to 0: 0 means "reference default" for max_new_tokens/temperature/top_p
     # (0 is invalid for them) and "disabled" for top_k (as in the reference CLI, generate.py:30).
     return SamplingParams(max_new_tokens=req.max_new_tokens or 20, is_greedy=req.is_greedy,
                           temperature=req.temperature or 1.0, top_p=req.top_p or 0.95, top_k=req.top_k,
-                          seed=req.seed or None, ignore_eos=req.ignore_eos, logprobs=logprobs, **pen).validate()
+                          seed=req.seed or None, ignore_eos=req.ignore_eos, logprobs=logprobs, **pen,
+                          **con).validate()
 
 
 def add_servicer(server: grpc.Server, servicer) -> None:
@@ -308,6 +328,9 @@ class EngineServicer:
     def _penalties(self):
         return getattr(getattr(self.driver, "engine", None), "penalties", None)
 
+    def _constraints(self):
+        return getattr(getattr(self.driver, "engine", None), "constraints", None)
+
     def _prompt_ids(self, req):
         from ..utils.tokenizer import encode
 
@@ -317,7 +340,7 @@ class EngineServicer:
 
     async def Generate(self, req, ctx):
         try:
-            params = _params(req, self._max_logprobs(), self._penalties())
+            params = _params(req, self._max_logprobs(), self._penalties(), self._constraints())
         except ValueError as e:
             await ctx.abort(grpc.StatusCode.INVALID_ARGUMENT, str(e))
         loop = asyncio.get_running_loop()
@@ -346,7 +369,7 @@ class EngineServicer:
 
     async def GenerateStream(self, req, ctx):
         try:
-            params = _params(req, self._max_logprobs(), self._penalties())
+            params = _params(req, self._max_logprobs(), self._penalties(), self._constraints())
         except ValueError as e:
             await ctx.abort(grpc.StatusCode.INVALID_ARGUMENT, str(e))
         loop = asyncio.get_running_loop()
@@ -406,6 +429,7 @@ class BrokerServicer:
                        temperature=req.temperature or 1.0, top_p=req.top_p or 0.95, top_k=req.top_k or 50,
                        request_id=rid, seed=req.seed or None, ignore_eos=req.ignore_eos, stream=stream,
                        logprobs=int(req.top_logprobs) if req.return_logprobs else None, **_penalty_fields(req),
+                       **_constraint_fields(req),
                        prompt_token_ids=list(req.prompt_token_ids) or None, deadline_s=deadline_s)
 
     def Generate(self, req, ctx):
@@ -414,7 +438,10 @@ class BrokerServicer:
 
         rid = req.request_id or new_request_id()
         remaining = ctx.time_remaining()
-        body = self._body(req, rid, deadline_s=remaining)
+        try:
+            body = self._body(req, rid, deadline_s=remaining)
+        except ValueError as e:  # logit_bias_ids / logit_bias_values of different lengths
+            ctx.abort(grpc.StatusCode.INVALID_ARGUMENT, str(e))
         t0 = time.perf_counter()
         self.broker.lpush(PQUEUE, body.model_dump_json(exclude_none=True))
         self.stats["requests"] += 1
@@ -439,8 +466,11 @@ class BrokerServicer:
 
         rid = req.request_id or new_request_id()
         remaining = ctx.time_remaining()
-        self.broker.lpush(PQUEUE, self._body(req, rid, stream=True, deadline_s=remaining).model_dump_json(
-            exclude_none=True))
+        try:
+            body = self._body(req, rid, stream=True, deadline_s=remaining)
+        except ValueError as e:
+            ctx.abort(grpc.StatusCode.INVALID_ARGUMENT, str(e))
+        self.broker.lpush(PQUEUE, body.model_dump_json(exclude_none=True))
         self.stats["requests"] += 1
         deadline = time.monotonic() + (remaining if remaining else self.timeout)
         while True:
@@ -484,7 +514,11 @@ class AioBrokerServicer(BrokerServicer):
         rid = req.request_id or new_request_id()
         t0 = time.perf_counter()
         remaining = ctx.time_remaining()
-        await self.client.lpush(PQUEUE, self._body(req, rid, deadline_s=remaining).model_dump_json(exclude_none=True))
+        try:
+            body = self._body(req, rid, deadline_s=remaining)
+        except ValueError as e:
+            await ctx.abort(grpc.StatusCode.INVALID_ARGUMENT, str(e))
+        await self.client.lpush(PQUEUE, body.model_dump_json(exclude_none=True))
         self.stats["requests"] += 1
         msg = await self.client.brpop(reply_key(rid), timeout=remaining if remaining else self.timeout)
         if msg is None:
@@ -504,8 +538,11 @@ class AioBrokerServicer(BrokerServicer):
 
         rid = req.request_id or new_request_id()
         remaining = ctx.time_remaining()
-        await self.client.lpush(PQUEUE, self._body(req, rid, stream=True, deadline_s=remaining).model_dump_json(
-            exclude_none=True))
+        try:
+            body = self._body(req, rid, stream=True, deadline_s=remaining)
+        except ValueError as e:
+            await ctx.abort(grpc.StatusCode.INVALID_ARGUMENT, str(e))
+        await self.client.lpush(PQUEUE, body.model_dump_json(exclude_none=True))
         self.stats["requests"] += 1
         deadline = time.monotonic() + (remaining if remaining else self.timeout)
         while True:

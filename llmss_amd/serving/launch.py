@@ -25,6 +25,10 @@ def add_engine_args(p):
                    help="serve repetition_penalty / presence_penalty / frequency_penalty: keeps every running "
                         "sequence's token counts on the device (max_num_seqs x vocab x 4 bytes); off: requests "
                         "that set one are rejected")
+    g.add_argument("--constraints", action="store_true",
+                   help="serve logit_bias / banned_token_ids / allowed_token_ids / min_tokens: keeps every running "
+                        "sequence's resolved token lists on the device (max_num_seqs x 8 KiB); off: requests that "
+                        "set one are rejected")
     g.add_argument("--dp", type=int, default=1,
                    help="data-parallel replicas: with torchrun, world = dp x tp (each replica's leader serves "
                         "from the broker); in a single process, one TP=1 replica per GPU behind a Router")
@@ -38,7 +42,8 @@ def _engine(model_path, tp, dev, args, tok=None):
     eng = LLMEngine(model, max_num_seqs=args.max_num_seqs, max_batched_tokens=args.max_batched_tokens,
                     block_size=args.block_size, max_model_len=args.max_model_len, use_graphs=not args.no_graphs,
                     eos_token_id=getattr(tok, "eos_token_id", None), max_logprobs=getattr(args, "max_logprobs", 0),
-                    penalties=bool(getattr(args, "penalties", False)))
+                    penalties=bool(getattr(args, "penalties", False)),
+                    constraints=bool(getattr(args, "constraints", False)))
     return eng, tok, model
 
 

@@ -12,7 +12,7 @@ import json
 import uuid
 from typing import Any, Dict, List, Optional
 
-from pydantic import BaseModel
+from pydantic import BaseModel, Field
 
 from ..engine.sampling import SamplingParams
 
@@ -38,6 +38,12 @@ class Request(BaseModel):
     repetition_penalty: float = 1.0
     presence_penalty: float = 0.0
     frequency_penalty: float = 0.0
+    # token constraints (SamplingParams; the serving engine needs --constraints, else the reply is an error).
+    # logit_bias maps token ids to biases in [-100, 100]; JSON object keys are strings, read back as ints here
+    logit_bias: Dict[int, float] = Field(default_factory=dict)
+    banned_token_ids: List[int] = Field(default_factory=list)
+    allowed_token_ids: List[int] = Field(default_factory=list)
+    min_tokens: int = 0
 
 
 class Response(BaseModel):
@@ -69,7 +75,9 @@ def to_sampling(req: Request) -> SamplingParams:
     return SamplingParams(max_new_tokens=req.max_new_tokens, is_greedy=req.is_greedy, temperature=req.temperature,
                           top_p=req.top_p, top_k=req.top_k, seed=req.seed, ignore_eos=req.ignore_eos,
                           logprobs=req.logprobs, repetition_penalty=req.repetition_penalty,
-                          presence_penalty=req.presence_penalty, frequency_penalty=req.frequency_penalty).validate()
+                          presence_penalty=req.presence_penalty, frequency_penalty=req.frequency_penalty,
+                          logit_bias=dict(req.logit_bias), banned_token_ids=list(req.banned_token_ids),
+                          allowed_token_ids=list(req.allowed_token_ids), min_tokens=req.min_tokens).validate()
 
 
 def dump_response(resp: Dict[str, Any]) -> str:

@@ -1,0 +1,319 @@
+"""Token constraints (logit_bias, banned / allowed tokens, min_tokens) through the engine on the CPU (tiny GPT-2 and
+Llama, fp32): every greedy token is the argmax of the oracle-constrained Hugging Face logits for the same prefix -
+also under chunked prefill, preemption, slot reuse and an abort, and combined with penalties in the defined order -
+plus the opt-in rules and TP=2 over gloo on both sampler routes. Every scenario derives its constraints from an
+unconstrained run that violates them."""
+import os
+import socket
+
+import pytest
+import torch
+import torch.multiprocessing as mp
+
+import constraint_cases as C
+import penalty_cases as P
+from helpers import save_hf_model
+from llmss_amd.engine import LLMEngine, SamplingParams
+from llmss_amd.engine.sampling import MAX_TOKEN_EDITS
+from llmss_amd.models.config import ModelConfig
+from llmss_amd.models.decoder import DecoderLM
+from llmss_amd.models.weights import load_hf_weights
+from llmss_amd.utils.checkpoint import CheckpointReader, weight_files
+
+TOL = 1e-4  # the facade parity tests' tolerance on fp32 logits
+NEW = 16
+PROMPTS = [[(3 * i + 7 * j) % 100 for j in range(5 + 2 * i)] for i in range(6)]
+
+
+def sp(n=NEW, **kw):
+    kw.setdefault("is_greedy", True)
+    kw.setdefault("ignore_eos", True)
+    return SamplingParams(max_new_tokens=n, **kw)
+
+
+def run(eng, prompts, sps, abort_after=None):
+    """Requests (in submission order) of a run to completion; ``abort_after`` = (steps, index) aborts one mid-run."""
+    rids = [eng.add_request(p, s) for p, s in zip(prompts, sps)]
+    done, steps = {}, 0
+    while eng.has_unfinished():
+        eng.step()
+        steps += 1
+        if abort_after and steps == abort_after[0]:
+            eng.abort(rids[abort_after[1]])
+        for r in eng.pop_finished():
+            done[r.id] = r
+    for r in eng.pop_finished():
+        done[r.id] = r
+    return [done[i] for i in rids]
+
+
+@pytest.fixture(scope="module")
+def ckpts(tmp_path_factory):
+    out = {}
+    for name in ("gpt2", "llama"):
+        d = str(tmp_path_factory.mktemp(name))
+        out[name] = (d, save_hf_model(name, d))
+    return out
+
+
+def _engine(d, **kw):
+    cfg = ModelConfig.from_pretrained(d)
+    w = load_hf_weights(cfg, CheckpointReader(weight_files(d)), 1, 0, device="cpu", dtype=torch.float32)
+    kw.setdefault("max_num_seqs", 4)
+    kw.setdefault("num_blocks", 64)
+    return LLMEngine(DecoderLM(cfg, w), block_size=4, **kw), cfg
+
+
+def verify(reqs, hf, cfg, eos=None):
+    """Every generated token is the argmax of the oracle-penalised, then oracle-constrained Hugging Face logits for
+    its prefix, and is not a forbidden one."""
+    for r in reqs:
+        if not r.output_ids:
+            continue
+        q = r.params
+        with torch.no_grad():
+            logits = hf(torch.tensor([r.prompt_ids + r.output_ids])).logits[0].double().numpy()
+        for t, tok in enumerate(r.output_ids):
+            row = logits[len(r.prompt_ids) - 1 + t, :cfg.vocab_size]
+            if q.has_penalties:
+                row = P.penalise_row(row, r.prompt_ids, r.output_ids[:t], q.repetition_penalty, q.presence_penalty,
+                                     q.frequency_penalty)
+            row = C.constrain_row(row, q, eos, t)
+            assert row[tok] > -float("inf") and row.max() - row[tok] <= TOL, \
+                (r.id, t, tok, int(row.argmax()), row.max() - row[tok])
+
+
+def derive(plain, V):
+    """Six requests' constraints, each one violated by the unconstrained greedy output ``plain[i]`` of its prompt."""
+    outs = [r.output_ids for r in plain]
+    absent = lambda i, n: [t for t in range(V) if t not in outs[i]][5:5 + n]  # noqa: E731
+    forced = absent(1, 1)[0]
+    allowed = absent(2, 5)
+    stop = outs[3][1]
+    assert forced not in outs[1] and not set(allowed) & set(outs[2]) and stop in outs[3][:2]
+    return [sp(banned_token_ids=list(dict.fromkeys(outs[0]))[:2]),  # the banned tokens do occur unconstrained
+            sp(logit_bias={forced: 100.0}),  # the forced token does not
+            sp(allowed_token_ids=allowed, logit_bias={allowed[0]: -0.5}),  # nor any of the allowed ones
+            sp(stop_token_ids=[stop], min_tokens=5),  # unconstrained, the stop token ends it after at most 2
+            sp(banned_token_ids=outs[4][:1], logit_bias={outs[4][1]: -100.0, absent(4, 1)[0]: 1.5},
+               repetition_penalty=1.3, presence_penalty=0.5, frequency_penalty=0.25),
+            sp()]
+
+
+def satisfied(reqs, plain):
+    q = [r.params for r in reqs]
+    o = [r.output_ids for r in reqs]
+    assert not set(q[0].banned_token_ids) & set(o[0])
+    assert set(o[1]) == set(q[1].logit_bias)
+    assert set(o[2]) <= set(q[2].allowed_token_ids)
+    if reqs[3].finish_reason != "abort":
+        assert len(o[3]) >= 5 and not set(o[3][:4]) & set(q[3].stop_token_ids)
+        assert reqs[3].finish_reason in ("stop", "length")
+    assert not set(q[4].banned_token_ids) & set(o[4]) and plain[4].output_ids[1] not in o[4]
+    assert o[5] == plain[5].output_ids[:len(o[5])]
+    for r, p in zip(reqs[:5], plain):
+        assert r.output_ids != p.output_ids[:len(r.output_ids)] or r.finish_reason == "abort"
+
+
+def idle(eng):
+    return (not eng._con_slot and sorted(eng._con_free) == list(range(eng.max_num_seqs))
+            and not eng._pen_slot and sorted(eng._pen_free) == list(range(eng.max_num_seqs)))
+
+
+@pytest.fixture(scope="module")
+def plains(ckpts):
+    out = {}
+    for name, (d, hf) in ckpts.items():
+        eng, cfg = _engine(d, max_num_seqs=8)
+        out[name] = run(eng, PROMPTS, [sp() for _ in PROMPTS])
+        verify(out[name], hf, cfg)
+    return out
+
+
+@pytest.mark.parametrize("name", ["gpt2", "llama"])
+def test_greedy_tokens_match_constrained_hf(ckpts, plains, name):
+    d, hf = ckpts[name]
+    eng, cfg = _engine(d, constraints=True, penalties=True, max_num_seqs=8)
+    assert eng.stats["constraint_state_bytes"] == 8 * (4 * MAX_TOKEN_EDITS + 4) * 4
+    plain = plains[name]
+    assert [r.output_ids for r in run(eng, PROMPTS, [sp() for _ in PROMPTS])] == [r.output_ids for r in plain]
+    stopped = run(eng, PROMPTS[3:4], [sp(stop_token_ids=[plain[3].output_ids[1]])])[0]
+    assert stopped.finish_reason == "stop" and len(stopped.output_ids) <= 2
+    reqs = run(eng, PROMPTS, derive(plain, cfg.vocab_size))
+    assert all(len(r.output_ids) == NEW for i, r in enumerate(reqs) if i != 3)
+    verify(reqs, hf, cfg)
+    satisfied(reqs, plain)
+    assert idle(eng)
+
+
+@pytest.mark.parametrize("how", ["chunked", "preempt", "reuse", "abort", "constraints_only"])
+def test_same_check_under(ckpts, plains, how):
+    d, hf = ckpts["llama"]
+    kw = {"chunked": dict(prefill_chunk=4), "preempt": dict(num_blocks=14), "reuse": dict(max_num_seqs=2),
+          "abort": {}, "constraints_only": {}}[how]
+    eng, cfg = _engine(d, constraints=True, penalties=True, **kw)
+    sps = derive(plains["llama"], cfg.vocab_size)
+    if how == "constraints_only":
+        eng, cfg = _engine(d, constraints=True)
+        sps[4] = sp(banned_token_ids=sps[4].banned_token_ids, logit_bias=sps[4].logit_bias)
+    reqs = run(eng, PROMPTS, sps, abort_after=(9, 1) if how == "abort" else None)
+    if how == "preempt":
+        assert eng.stats["preemptions"] > 0
+    if how == "abort":
+        assert reqs[1].finish_reason == "abort" and 0 < len(reqs[1].output_ids) < NEW
+    assert all(len(r.output_ids) == NEW for i, r in enumerate(reqs) if r.finish_reason != "abort" and i != 3)
+    verify(reqs, hf, cfg)
+    satisfied(reqs, plains["llama"])
+    assert idle(eng)
+
+
+@pytest.mark.parametrize("name", ["gpt2", "llama"])
+def test_min_tokens_holds_eos_back(ckpts, plains, name):
+    """The engine's EOS is the token the unconstrained greedy run emits at output position k >= 1: that run ends
+    there with reason eos, the min_tokens = k + 3 run goes on for at least k + 3 tokens."""
+    d, hf = ckpts[name]
+    out = plains[name][0].output_ids
+    k = next(i for i in range(1, NEW) if out[i] not in out[:i])
+    eos = out[k]
+    eng, cfg = _engine(d, constraints=True, eos_token_id=eos)
+    a, b, c = run(eng, PROMPTS[:1] * 3, [sp(ignore_eos=False), sp(ignore_eos=False, min_tokens=k + 3),
+                                         sp(ignore_eos=True, min_tokens=k + 3)])
+    assert a.finish_reason == "eos" and a.output_ids == out[:k + 1]
+    assert len(b.output_ids) >= k + 3 and eos not in b.output_ids[:k + 2] and b.output_ids[:k] == out[:k]
+    assert b.finish_reason in ("eos", "length") and (b.finish_reason == "length" or b.output_ids[-1] == eos)
+    assert c.output_ids == out  # EOS ignored: nothing to hold back
+    verify([a, b, c], hf, cfg, eos=eos)
+    assert idle(eng)
+
+
+def test_mixed_batch_defaults_unchanged(ckpts, plains):
+    d, hf = ckpts["llama"]
+    off, cfg = _engine(d)
+    on, _ = _engine(d, constraints=True)
+    plain = plains["llama"]
+    sps = derive(plain, cfg.vocab_size)
+    mixed = run(on, PROMPTS[:4], [sp(), sps[1], sp(), sps[3]])
+    assert mixed[0].output_ids == plain[0].output_ids and mixed[2].output_ids == plain[2].output_ids
+    assert mixed[1].output_ids != plain[1].output_ids
+    verify(mixed, hf, cfg)
+    seeded = [sp(temperature=0.9, top_k=20, top_p=0.9, seed=5 + i, is_greedy=False) for i in range(4)]
+    a = run(off, PROMPTS[:4], seeded)
+    b = run(on, PROMPTS[:4], [SamplingParams(**s.__dict__) for s in seeded])
+    assert [r.output_ids for r in a] == [r.output_ids for r in b]
+    # sampled rows keep to their constraints too
+    ban = sorted({t for r in a for t in r.output_ids[:3]})
+    s2 = [SamplingParams(**{**s.__dict__, "banned_token_ids": ban}) for s in seeded]
+    for r in run(on, PROMPTS[:4], s2):
+        assert len(r.output_ids) == NEW and not set(ban) & set(r.output_ids)
+
+
+def test_opt_in_and_validation(ckpts):
+    d, _ = ckpts["llama"]
+    off, cfg = _engine(d)
+    V = cfg.vocab_size
+    assert off.constraints is False and off.fingerprint()["constraints"] is False and off.con_state is None
+    assert "constraint_state_bytes" not in off.stats
+    for kw in (dict(logit_bias={1: 1.0}), dict(banned_token_ids=[1]), dict(allowed_token_ids=[1, 2]),
+               dict(min_tokens=1)):
+        with pytest.raises(ValueError, match="constraints=True"):
+            off.add_request([1, 2, 3], sp(n=2, **kw))
+    assert not off.has_unfinished() and not off.requests  # the rejected requests left nothing behind
+    off.add_request([1, 2, 3], sp(n=2))  # the defaults are no constraint
+    on, _ = _engine(d, constraints=True)
+    assert on.fingerprint()["constraints"] is True and on.fingerprint()["penalties"] is False
+    E = MAX_TOKEN_EDITS
+    for kw in (dict(logit_bias={V: 1.0}), dict(banned_token_ids=[V]), dict(allowed_token_ids=[0, V + 1]),  # range
+               dict(logit_bias={1: 101.0}), dict(banned_token_ids=[1, 1]), dict(min_tokens=3),  # validate()
+               dict(allowed_token_ids=[1, 2], banned_token_ids=[1, 2])):  # nothing left
+        with pytest.raises(ValueError):
+            on.add_request([1, 2, 3], sp(n=2, **kw))
+    if V > E:  # capacity
+        with pytest.raises(ValueError):
+            on.add_request([1, 2, 3], sp(n=2, banned_token_ids=list(range(E + 1))))
+    with pytest.raises(ValueError):  # the early list has no token left: EOS is the one allowed token
+        on.add_request([1, 2, 3], sp(n=2, allowed_token_ids=[on.eos if on.eos is not None else 0],
+                                     stop_token_ids=[on.eos if on.eos is not None else 0], min_tokens=1,
+                                     ignore_eos=False))
+    assert not on.has_unfinished() and not on.requests and idle(on)
+
+
+# ---------------------------------------------------------------------------------------- TP=2 over gloo
+def _free_port():
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    p = s.getsockname()[1]
+    s.close()
+    return p
+
+
+def _tp_runs(sps):
+    """Two runs: rows the vocab-parallel candidate sampler takes (greedy, top-k <= 64), then a batch with an
+    unrestricted row, which goes through the gathered logits."""
+    mk = lambda s, **kw: SamplingParams(**{**s.__dict__, **kw})  # noqa: E731
+    cand = [mk(sps[i], is_greedy=i % 2 == 0, temperature=0.9, top_k=20, top_p=0.9, seed=11 + i) for i in range(4)]
+    gath = [mk(sps[i + 1], is_greedy=False, temperature=0.9, top_k=0 if i == 0 else 20, top_p=0.9, seed=3 + i)
+            for i in range(4)]
+    return cand, gath
+
+
+def _worker(rank, world, port, ckpt, sps, q):
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
+                      LOCAL_RANK=str(rank))
+    torch.set_num_threads(1)
+    from llmss_amd import ops
+    from llmss_amd.engine import LLMEngine, build_model
+    from llmss_amd.parallel.dist import initialize_distributed
+
+    tp, r, w = initialize_distributed(backend="gloo")
+    eng = LLMEngine(build_model(ckpt, tp, "fp32", "cpu"), max_num_seqs=4, block_size=4, num_blocks=64,
+                    check_tokens=True, penalties=True, constraints=True)
+    assert eng.dist_sampling
+    widths = []
+    inner = ops.apply_token_edits
+    ops.apply_token_edits = lambda lg, *a, **k: (widths.append((lg.shape[1], a[5])), inner(lg, *a, **k))[1]
+    res = []
+    for run_sps in _tp_runs(sps):
+        res.append([x.output_ids for x in run(eng, PROMPTS[:4], run_sps)])
+        res.append(sorted(set(widths)))
+        del widths[:]
+    assert idle(eng)
+    allres = tp.all_gather_object(res[0::2])
+    assert all(a == res[0::2] for a in allres), "ranks disagree on tokens"
+    if r == 0:
+        q.put(res)
+    torch.distributed.barrier()
+    torch.distributed.destroy_process_group()
+
+
+def test_tp2_gloo_matches_single(tmp_path):
+    d = str(tmp_path / "llama")
+    save_hf_model("llama", d, vocab=101)  # 101 % 2 != 0: the padded vocab-parallel head
+    from llmss_amd.engine import build_model
+
+    eng = LLMEngine(build_model(d, None, "fp32", "cpu"), max_num_seqs=8, block_size=4, num_blocks=64, penalties=True,
+                    constraints=True)
+    plain = run(eng, PROMPTS, [sp() for _ in PROMPTS])
+    sps = derive(plain, 101)
+    # tokens of both shards in one request: rank 0 holds the tokens below 51
+    sps[0] = sp(banned_token_ids=sorted(set(plain[0].output_ids[:2]) | {3, 97}), logit_bias={50: 2.0, 51: -2.0, 100: 1.0})
+    ref = [[x.output_ids for x in run(eng, PROMPTS[:4], s)] for s in _tp_runs(sps)]
+    for outs, s in zip(ref, _tp_runs(sps)):
+        for o, q_ in zip(outs, s):
+            assert not set(q_.banned_token_ids) & set(o)
+            assert not q_.allowed_token_ids or set(o) <= set(q_.allowed_token_ids)
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_worker, args=(r, 2, port, d, sps, q)) for r in range(2)]
+    for p in procs:
+        p.start()
+    got = q.get(timeout=240)
+    for p in procs:
+        p.join(timeout=60)
+        assert p.exitcode == 0
+    cand_tokens, cand_calls, gath_tokens, gath_calls = got
+    assert cand_tokens == ref[0] and gath_tokens == ref[1]
+    # rank 0's launches: its shard of the padded head (fewer columns than the vocabulary) at lo = 0 on the
+    # vocab-parallel route, whole rows on the gathered one
+    assert cand_calls and all(wd < 101 and lo == 0 for wd, lo in cand_calls), cand_calls
+    assert any(wd >= 101 and lo == 0 for wd, lo in gath_calls), gath_calls
