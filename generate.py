@@ -55,6 +55,9 @@ def get_args(argv=None):
                         help="the only token ids that are sampled")
     parser.add_argument("--min_tokens", type=int, default=0,
                         help="EOS is not sampled before this many tokens were generated")
+    parser.add_argument("--min_p", type=float, default=0.0,
+                        help="[0, 1]: after top-k and top-p, keep only tokens at least this likely relative to the most "
+                             "likely one (0: off)")
     return parser.parse_args(argv)
 
 
@@ -123,7 +126,8 @@ def recompute_generate(model, prompts, params, eos, lp_out=None):
             plogits = ops.apply_token_edits(plogits, *edits, torch.zeros(n, dtype=torch.int32, device=dev),
                                             torch.tensor([len(outs[i]) for i in live], dtype=torch.int32, device=dev),
                                             0, V)
-        tok = ops.sample(plogits, temp, topk, topp, seeds, vocab=model.cfg.vocab_size)
+        lnmp = torch.full((n,), params.k_ln_min_p, dtype=torch.float32, device=dev) if params.has_min_p else None
+        tok = ops.sample(plogits, temp, topk, topp, seeds, vocab=model.cfg.vocab_size, ln_min_p=lnmp)
         if lp_out is not None:
             nlp = params.logprobs
             lp, top, tids = (x.cpu().tolist() for x in ops.token_logprobs(logits, model.cfg.vocab_size, tok, nlp))
@@ -152,6 +156,7 @@ def main(argv=None):
     assert isinstance(logit_bias, dict), "Value of logit_bias should be a JSON object."
     logit_bias = {int(k): float(v) for k, v in logit_bias.items()}  # JSON object keys are strings
     assert 0 <= args.min_tokens <= args.max_new_tokens, "Value of min_tokens is not valid."
+    assert 0.0 <= args.min_p <= 1.0, "Value of min_p is not valid."
 
     from llmss_amd.engine import LLMEngine, SamplingParams, build_model
     from llmss_amd.parallel.dist import initialize_distributed
@@ -177,7 +182,8 @@ def main(argv=None):
                             logprobs=args.logprobs, repetition_penalty=args.repetition_penalty,
                             presence_penalty=args.presence_penalty, frequency_penalty=args.frequency_penalty,
                             logit_bias=logit_bias, banned_token_ids=args.banned_token_ids,
-                            allowed_token_ids=args.allowed_token_ids, min_tokens=args.min_tokens).validate()
+                            allowed_token_ids=args.allowed_token_ids, min_tokens=args.min_tokens,
+                            min_p=args.min_p).validate()
     eos = getattr(tokenizer, "eos_token_id", None)
     prompts = [encode(tokenizer, p) for p in args.prompts]
     max_len = model.cfg.max_position_embeddings
@@ -189,7 +195,8 @@ def main(argv=None):
                            # --logprobs 0 still needs the kernel, hence an engine with N >= 1
                            max_logprobs=0 if args.logprobs is None else max(1, args.logprobs),
                            # the states only when a flag differs from its default
-                           penalties=params.has_penalties, constraints=params.has_constraints)
+                           penalties=params.has_penalties, constraints=params.has_constraints,
+                           min_p=params.has_min_p)
         per = [SamplingParams(**{**params.__dict__, "seed": seed + i}) for i in range(len(prompts))]
         if args.logprobs is None:
             outputs = engine.generate(prompts, per)

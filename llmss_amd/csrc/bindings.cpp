@@ -34,7 +34,8 @@ void gemm_big_set_group(int g);
 void launch_cand_topk(const void* logits, int64_t ld, int B, int vl, int lo, int V, const void* temperature,
                       const void* top_k, int K, int KC, void* pack, int64_t ldp, hipStream_t st, int shards);
 void launch_sample_cand(const void* pack, int64_t ldp, int B, int groups, int KC, const void* temperature,
-                        const void* top_k, const void* top_p, const void* seeds, void* out, void* out2, hipStream_t st);
+                        const void* top_k, const void* top_p, const void* seeds, void* out, void* out2, hipStream_t st,
+                        const void* ln_min_p = nullptr);
 void launch_ce_loss(const void* logits, int64_t ld, bool fp32, const void* labels, int T, int V, void* loss,
                     hipStream_t st);
 void launch_token_logprobs(const void* logits, int64_t ld, bool fp32, int B, int width, int lo, int V,
@@ -79,7 +80,8 @@ void launch_add_norm_partial(const void* part, int S, int64_t slab, const void* 
                              void* res_out, const void* w, const void* b, void* y, int64_t y_stride, int T, int H,
                              float eps, bool rms, hipStream_t st, void* q8, void* s8);
 void launch_sample(const void* logits, int64_t ld, bool fp32_logits, int B, int V, const void* temperature,
-                   const void* top_k, const void* top_p, const void* seeds, void* out, void* out2, hipStream_t st);
+                   const void* top_k, const void* top_p, const void* seeds, void* out, void* out2, hipStream_t st,
+                   const void* ln_min_p = nullptr);
 void launch_quant_fp8_rows(const void* w, void* q, void* scale, int64_t N, int64_t K, hipStream_t st);
 void launch_quant_fp8_rows_ld(const void* x, int64_t ldx, void* q, void* scale, int64_t M, int64_t K, hipStream_t st);
 void launch_dequant_fp8_rows(const void* q, const void* scale, void* w, int64_t N, int64_t K, hipStream_t st);
@@ -136,6 +138,13 @@ PYBIND11_MODULE(_C, m) {
   m.def("sample_cand", [](uintptr_t pack, int64_t ldp, int B, int groups, int KC, uintptr_t temp, uintptr_t topk,
                           uintptr_t topp, uintptr_t seeds, uintptr_t out, uintptr_t out2, uintptr_t st) {
     launch_sample_cand(CP(pack), ldp, B, groups, KC, CP(temp), CP(topk), CP(topp), CP(seeds), P(out), P(out2), S(st));
+  });
+  // + ln_min_p [B] fp32 (0: no min-p floor, the call above)
+  m.def("sample_cand", [](uintptr_t pack, int64_t ldp, int B, int groups, int KC, uintptr_t temp, uintptr_t topk,
+                          uintptr_t topp, uintptr_t seeds, uintptr_t out, uintptr_t out2, uintptr_t st,
+                          uintptr_t lnmp) {
+    launch_sample_cand(CP(pack), ldp, B, groups, KC, CP(temp), CP(topk), CP(topp), CP(seeds), P(out), P(out2), S(st),
+                       CP(lnmp));
   });
   m.def("ce_loss", [](uintptr_t lg, int64_t ld, bool fp32, uintptr_t lab, int T, int V, uintptr_t loss, uintptr_t st) {
     launch_ce_loss(CP(lg), ld, fp32, CP(lab), T, V, P(loss), S(st));
@@ -272,6 +281,12 @@ PYBIND11_MODULE(_C, m) {
   m.def("sample", [](uintptr_t logits, int64_t ld, bool fp32, int B, int V, uintptr_t temp, uintptr_t topk,
                      uintptr_t topp, uintptr_t seeds, uintptr_t out, uintptr_t out2, uintptr_t st) {
     launch_sample(CP(logits), ld, fp32, B, V, CP(temp), CP(topk), CP(topp), CP(seeds), P(out), P(out2), S(st));
+  });
+  // + ln_min_p [B] fp32 (0: no min-p floor, the call above)
+  m.def("sample", [](uintptr_t logits, int64_t ld, bool fp32, int B, int V, uintptr_t temp, uintptr_t topk,
+                     uintptr_t topp, uintptr_t seeds, uintptr_t out, uintptr_t out2, uintptr_t st, uintptr_t lnmp) {
+    launch_sample(CP(logits), ld, fp32, B, V, CP(temp), CP(topk), CP(topp), CP(seeds), P(out), P(out2), S(st),
+                  CP(lnmp));
   });
   m.def("quant_fp8_rows", [](uintptr_t w, uintptr_t q, uintptr_t scale, int64_t N, int64_t K, uintptr_t st) {
     launch_quant_fp8_rows(CP(w), P(q), P(scale), N, K, S(st));

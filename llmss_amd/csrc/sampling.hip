@@ -10,6 +10,14 @@
 // prefix sum. Noise is Philox-4x32-10 keyed by the per-row 64-bit seed and counted by token
 // index, so every tensor-parallel rank - which holds the same all-gathered logits - draws the
 // same token with no broadcast (reference broadcasts the sampled token every step, C7/C11).
+//
+// Min-p (MINP variants, chosen when the launcher gets a non-null ln_min_p): after top-k and top-p - the nucleus
+// is computed without the floor - a non-greedy row also drops every token whose scaled logit is below
+// mx + ln_min_p[b], mx = the row's maximum scaled logit, i.e. whose probability is below min_p times the most
+// likely token's. ln_min_p is fp32 ln(min_p), rounded once on the host (-inf: off); the kernels take no
+// logarithm, the floor is one fp32 add and the comparison is >= on floats, so the boundary is exact and the same
+// on every rank. The maxima always survive. The variant is a template parameter: the instantiations without it
+// are the code they were.
 #include "common.h"
 #include <cstdlib>
 
@@ -84,12 +92,13 @@ __device__ unsigned radix_select(const T* row, int V, float scale, float mx, uns
   return prefix;
 }
 
-template <typename T>
+template <typename T, bool MINP>
 __global__ __launch_bounds__(1024) void sample_kernel(const T* __restrict__ logits, int64_t ld, int V,
                                                       const float* __restrict__ temperature,
                                                       const int* __restrict__ top_k, const float* __restrict__ top_p,
                                                       const int64_t* __restrict__ seeds, int64_t* __restrict__ out,
-                                                      int64_t* __restrict__ out2) {
+                                                      int64_t* __restrict__ out2,
+                                                      const float* __restrict__ ln_min_p) {
   __shared__ float hist[256];
   __shared__ float red[32];
   __shared__ int redi[32];
@@ -120,6 +129,13 @@ __global__ __launch_bounds__(1024) void sample_kernel(const T* __restrict__ logi
       z = block_sum(z, red);
       const unsigned tp = radix_select(row, V, scale, mx, thr, p * z, 1, hist, red);
       thr = tp > thr ? tp : thr;
+    }
+    if constexpr (MINP) {
+      // the floor as a key. Keys order -0.0 below +0.0 while the floats compare equal: a floor of +0.0 takes the
+      // key of -0.0, so that x >= floor holds as it does on floats. NaN (mx = +inf with the floor off): no floor.
+      const float fl = mx + ln_min_p[b];
+      const unsigned km = fkey(fl == 0.f ? -0.f : fl);
+      if (fl == fl && km > thr) thr = km;
     }
   }
   // argmax of (x + gumbel) over kept tokens (greedy: plain argmax, lowest index on ties)
@@ -253,12 +269,13 @@ __device__ __attribute__((noinline)) void sv3_sort(Sv3Smem& sm, int n) {
 // over the row re-reads it from LDS (ds_read_b128, conflict-free lane-linear chunks) instead.
 constexpr int SV3_LROW_CHUNKS = 7168;  // 112 KiB row + ~40 KiB Sv3Smem < 160 KiB LDS
 
-template <int CPT, bool LROW>
+template <int CPT, bool LROW, bool MINP>
 __global__ __launch_bounds__(1024) void sample_v3_kernel(const bf16_t* __restrict__ logits, int64_t ld, int V,
                                                          const float* __restrict__ temperature,
                                                          const int* __restrict__ top_k, const float* __restrict__ top_p,
                                                          const int64_t* __restrict__ seeds, int64_t* __restrict__ out,
-                                                         int64_t* __restrict__ out2) {
+                                                         int64_t* __restrict__ out2,
+                                                         const float* __restrict__ ln_min_p) {
   __shared__ Sv3Smem sm;
   __shared__ __attribute__((aligned(16))) u16x8 srow[LROW ? SV3_LROW_CHUNKS : 1];
   const int b = blockIdx.x, tid = threadIdx.x;
@@ -415,6 +432,8 @@ FOR_ELEMS(i) {
       }
       thr = fmaxf(thr, tp);
     }
+    // min-p: also with neither top-k nor top-p (thr = -inf, no histogram built). fmaxf drops a NaN floor.
+    if constexpr (MINP) thr = fmaxf(thr, mx + ln_min_p[b]);
   }
   // Gumbel-max over the kept set (greedy: plain argmax, lowest index on ties)
   const unsigned long long seed = seeds ? (unsigned long long)seeds[b] : 0ull;
@@ -458,30 +477,42 @@ FOR_ELEMS(i) {
 }
 
 void launch_sample(const void* logits, int64_t ld, bool fp32_logits, int B, int V, const void* temperature,
-                   const void* top_k, const void* top_p, const void* seeds, void* out, void* out2, hipStream_t st) {
+                   const void* top_k, const void* top_p, const void* seeds, void* out, void* out2, hipStream_t st,
+                   const void* ln_min_p) {
   if (B == 0) return;
   const int chunks = (V + 7) / 8;
   if (!fp32_logits && ld % 8 == 0 && (uintptr_t)logits % 16 == 0 && chunks <= SV3_LROW_CHUNKS) {
-#define SV3(CPT_, LROW_)                                                                                            \
-  sample_v3_kernel<CPT_, LROW_><<<B, 1024, 0, st>>>((const bf16_t*)logits, ld, V, (const float*)temperature,      \
-                                                    (const int*)top_k, (const float*)top_p, (const int64_t*)seeds, \
-                                                    (int64_t*)out, (int64_t*)out2)
+#define SV3_(CPT_, LROW_, MINP_)                                                                                  \
+  sample_v3_kernel<CPT_, LROW_, MINP_><<<B, 1024, 0, st>>>(                                                        \
+      (const bf16_t*)logits, ld, V, (const float*)temperature, (const int*)top_k, (const float*)top_p,             \
+      (const int64_t*)seeds, (int64_t*)out, (int64_t*)out2, (const float*)ln_min_p)
+#define SV3(CPT_, LROW_)                   \
+  do {                                     \
+    if (ln_min_p) SV3_(CPT_, LROW_, true); \
+    else SV3_(CPT_, LROW_, false);         \
+  } while (0)
     // register-resident rows up to CPT 4 (LDS rows measured 2-10 % slower there, profiles/r5_sampler); CPT 8
     // would spill, so its row lives in LDS
     if (chunks <= 2048) SV3(2, false);
     else if (chunks <= 4096) SV3(4, false);
     else SV3(8, true);
 #undef SV3
+#undef SV3_
     HIP_CHECK_LAUNCH();
     return;
   }
-  if (fp32_logits)
-    sample_kernel<float><<<B, 1024, 0, st>>>((const float*)logits, ld, V, (const float*)temperature, (const int*)top_k,
-                                             (const float*)top_p, (const int64_t*)seeds, (int64_t*)out, (int64_t*)out2);
-  else
-    sample_kernel<bf16_t><<<B, 1024, 0, st>>>((const bf16_t*)logits, ld, V, (const float*)temperature,
-                                              (const int*)top_k, (const float*)top_p, (const int64_t*)seeds,
-                                              (int64_t*)out, (int64_t*)out2);
+#define SK(T_, MINP_)                                                                                          \
+  sample_kernel<T_, MINP_><<<B, 1024, 0, st>>>((const T_*)logits, ld, V, (const float*)temperature,             \
+                                               (const int*)top_k, (const float*)top_p, (const int64_t*)seeds,   \
+                                               (int64_t*)out, (int64_t*)out2, (const float*)ln_min_p)
+  if (fp32_logits) {
+    if (ln_min_p) SK(float, true);
+    else SK(float, false);
+  } else {
+    if (ln_min_p) SK(bf16_t, true);
+    else SK(bf16_t, false);
+  }
+#undef SK
   HIP_CHECK_LAUNCH();
 }
 
@@ -495,6 +526,9 @@ void launch_sample(const void* logits, int64_t ld, bool fp32_logits, int B, int 
 // mass, Philox Gumbel-max keyed by the GLOBAL token index) on the union. For greedy rows and rows
 // with 1 <= top_k <= K the global kept set is inside that union, so the token equals the v3
 // sampler's on the gathered row bit for bit (same mx, same masses, same noise).
+// Min-p keeps that: the maximum over the union is the row's maximum, because every shard contributes its largest
+// elements, so the floor mx + ln_min_p is the full row's; and the floor only removes tokens, so the kept set of
+// those rows stays inside the union. cand_topk and the choice of rows (ops.cand_ok) are unchanged by it.
 // ---------------------------------------------------------------------------------------------
 constexpr int CAND_THREADS = 1024;
 
@@ -643,16 +677,17 @@ __global__ __launch_bounds__(CAND_THREADS) void cand_topk_kernel(const bf16_t* _
 
 constexpr int SCAND_MAX = 2048;  // gathered candidates per row (tp * KC)
 
+template <bool MINP>
 __global__ __launch_bounds__(256) void sample_cand_kernel(const float* __restrict__ pack, int64_t ldp, int groups,
                                                           int KC, const float* __restrict__ temperature,
                                                           const int* __restrict__ top_k,
                                                           const float* __restrict__ top_p,
                                                           const int64_t* __restrict__ seeds,
-                                                          int64_t* __restrict__ out, int64_t* __restrict__ out2) {
+                                                          int64_t* __restrict__ out, int64_t* __restrict__ out2,
+                                                          const float* __restrict__ ln_min_p) {
   __shared__ float v[SCAND_MAX];
   __shared__ int id[SCAND_MAX];
   __shared__ float sv[SCAND_MAX];  // sorted (value desc, index asc)
-  __shared__ int sid[SCAND_MAX];
   __shared__ float cv[SCAND_MAX];  // candidates >= the top-k boundary (unordered)
   __shared__ int cid[SCAND_MAX];
   __shared__ unsigned hist[256];
@@ -737,7 +772,6 @@ __global__ __launch_bounds__(256) void sample_cand_kernel(const float* __restric
         r += (c > a || (c == a && cid[j] < ai)) ? 1 : 0;
       }
       sv[r] = a;
-      sid[r] = ai;
     }
     __syncthreads();
     if (t == 0) {
@@ -766,6 +800,7 @@ __global__ __launch_bounds__(256) void sample_cand_kernel(const float* __restric
     }
     __syncthreads();
     thr = thr_s;
+    if constexpr (MINP) thr = fmaxf(thr, mx + ln_min_p[b]);  // mx over the union = the row's maximum
   }
   const unsigned long long seed = seeds ? (unsigned long long)seeds[b] : 0ull;
   const unsigned s0 = (unsigned)seed, s1 = (unsigned)(seed >> 32);
@@ -821,11 +856,16 @@ void launch_cand_topk(const void* logits, int64_t ld, int B, int vl, int lo, int
 }
 
 void launch_sample_cand(const void* pack, int64_t ldp, int B, int groups, int KC, const void* temperature,
-                        const void* top_k, const void* top_p, const void* seeds, void* out, void* out2, hipStream_t st) {
+                        const void* top_k, const void* top_p, const void* seeds, void* out, void* out2, hipStream_t st,
+                        const void* ln_min_p) {
   if (B == 0) return;
   if (groups * KC > SCAND_MAX) throw std::runtime_error("sample_cand: too many candidates per row");
-  sample_cand_kernel<<<B, 256, 0, st>>>((const float*)pack, ldp, groups, KC, (const float*)temperature,
-                                        (const int*)top_k, (const float*)top_p, (const int64_t*)seeds, (int64_t*)out,
-                                        (int64_t*)out2);
+#define SC(MINP_)                                                                                                 \
+  sample_cand_kernel<MINP_><<<B, 256, 0, st>>>((const float*)pack, ldp, groups, KC, (const float*)temperature,     \
+                                               (const int*)top_k, (const float*)top_p, (const int64_t*)seeds,      \
+                                               (int64_t*)out, (int64_t*)out2, (const float*)ln_min_p)
+  if (ln_min_p) SC(true);
+  else SC(false);
+#undef SC
   HIP_CHECK_LAUNCH();
 }

@@ -99,19 +99,22 @@ class _DecodeBuffers:
     ``penalties`` appends ``pslot`` (i32, after the block tables) and ``rep`` / ``pres`` / ``freq`` (f32, after top_p) to
     the staging blob - without it every offset is as before - and keeps the penalised logits, one static buffer per
     logits width (``pen_out``). ``constraints`` appends ``cslot`` and ``cnout`` (i32, after ``pslot`` when both are on)
-    and keeps the constrained logits the same way (``con_out``)."""
+    and keeps the constrained logits the same way (``con_out``). ``min_p`` appends ``lnmp`` (f32, the rows' ln(min_p),
+    at the end of the f32 section: after ``freq`` when penalties are on)."""
 
     def __init__(self, max_b: int, max_blocks: int, device, max_logprobs: int = 0, penalties: bool = False,
-                 constraints: bool = False):
+                 constraints: bool = False, min_p: bool = False):
         B, MB = max_b, max_blocks
         self.max_b, self.max_blocks = B, MB
         self.penalties = bool(penalties)
         self.constraints = bool(constraints)
+        self.min_p = bool(min_p)
         pin = torch.cuda.is_available() and device.type == "cuda"
-        # ids|pos|slots|seeds (i64) | ctx|topk|bt[|pslot][|cslot|cnout] (i32) | temp|topp[|rep|pres|freq] (f32)
+        # ids|pos|slots|seeds (i64) | ctx|topk|bt[|pslot][|cslot|cnout] (i32) | temp|topp[|rep|pres|freq][|lnmp] (f32)
         self.o32 = 4 * B * 8
         self.of32 = self.o32 + (2 * B + B * MB + (B if penalties else 0) + (2 * B if constraints else 0)) * 4
-        nbytes = self.of32 + (5 if penalties else 2) * B * 4
+        self.o_lnmp = (5 if penalties else 2) * B  # f32 words before lnmp
+        nbytes = self.of32 + (self.o_lnmp + (B if min_p else 0)) * 4
         self.h = [torch.zeros(nbytes, dtype=torch.uint8, pin_memory=pin) for _ in range(2)]
         self.d = torch.zeros(nbytes, dtype=torch.uint8, device=device)
         self.d_i64 = self.d[:self.o32].view(torch.int64)
@@ -132,6 +135,7 @@ class _DecodeBuffers:
             self.cslot = self.d_i32[self.o_con:self.o_con + B]
             self.cnout = self.d_i32[self.o_con + B:self.o_con + 2 * B]
             self._con_out = {}
+        self.lnmp = self.d_f32[self.o_lnmp:self.o_lnmp + B] if min_p else None
         N = self.max_logprobs = max_logprobs
         if N > 0:
             self.lp_f = torch.zeros(max_b, 1 + N, dtype=torch.float32, device=device)
@@ -161,11 +165,12 @@ class _DecodeBuffers:
             self._con_out[key] = torch.zeros(self.max_b, like.shape[1], dtype=like.dtype, device=like.device)
         return self._con_out[key][:b]
 
-    def fill(self, k, b_pad, ids, pos, slots, seeds, ctx, topk, bt, temp, topp, pen=None, con=None):
+    def fill(self, k, b_pad, ids, pos, slots, seeds, ctx, topk, bt, temp, topp, pen=None, con=None, lnmp=None):
         """Stage one step's inputs in set k and copy them to the device. ``ids=None``: the input ids
         are the previous step's sampled tokens, copied on the device (same rows). ``pen``: the rows' (penalty slot,
         repetition, presence, frequency) arrays; padded rows get slot -1. ``con``: the rows' (constraint slot, tokens
-        generated so far) arrays; padded rows get slot -1."""
+        generated so far) arrays; padded rows get slot -1. ``lnmp``: the rows' ln(min_p); padded rows (and every row
+        without it) get -inf, no floor."""
         n = len(pos)
         B, MB = self.max_b, self.max_blocks
         h = self.h[k]
@@ -201,6 +206,10 @@ class _DecodeBuffers:
             if con is not None:
                 cs[:n] = con[0]
                 cs[B:B + n] = con[1]
+        if self.min_p:
+            hf[self.o_lnmp:self.o_lnmp + b_pad] = -np.inf
+            if lnmp is not None:
+                hf[self.o_lnmp:self.o_lnmp + n] = lnmp
         self.d.copy_(h, non_blocking=True)
         if ids is None:
             self.ids[:n].copy_(self.out[:n])
@@ -213,8 +222,12 @@ class LLMEngine:
                  graph_buckets: Optional[Sequence[int]] = None, check_tokens: Optional[bool] = None,
                  autotune: Optional[bool] = None, prefill_chunk: Optional[int] = None,
                  kv_dtype: Optional[str] = None, max_logprobs: int = 0, penalties: bool = False,
-                 constraints: bool = False):
+                 constraints: bool = False, min_p: bool = False):
         self.model = model
+        # launch-time opt-in: True stages every row's ln(min_p) with the step's inputs and samples through the MINP
+        # variants of the sampler kernels (csrc/sampling.hip); False leaves graphs, buffers and steps as they are and
+        # rejects requests that ask for a min_p floor. There is no per-sequence state.
+        self.min_p = bool(min_p)
         # launch-time opt-in: True keeps every running sequence's resolved token constraints (logit_bias, banned /
         # allowed tokens, min_tokens: two lists of at most MAX_TOKEN_EDITS (token, value) pairs) on the device and runs
         # the constraint launch between the penalties and the sampler; False leaves graphs, buffers and steps as they
@@ -322,7 +335,7 @@ class LLMEngine:
         self.decode_schedule: Dict[int, str] = {}
         self.tp.check_consistent("LLMEngine", self.fingerprint())
         self.buf = _DecodeBuffers(self.buckets[-1], self.max_blocks, self.device, self.max_logprobs, self.penalties,
-                                  self.constraints) if self.is_gpu else None
+                                  self.constraints, self.min_p) if self.is_gpu else None
         if self.is_gpu:
             _hip_ops.reserve_workspace(self.device, 64 << 20)
             for b in self.decode_batch_sizes():
@@ -429,7 +442,7 @@ class LLMEngine:
                 "buckets": list(self.buckets), "graphs": bool(self.use_graphs),
                 "async_decode": self.async_decode, "eos": self.eos, "prefill_chunk": self.prefill_chunk, "window": self.window,
                 "dist_sampling": self.dist_sampling, "max_logprobs": self.max_logprobs, "kv_fp8": bool(self.model.kv_fp8),
-                "penalties": self.penalties, "constraints": self.constraints,
+                "penalties": self.penalties, "constraints": self.constraints, "min_p": self.min_p,
                 "overlap_rows": self.model.overlap_rows, "bucket_bytes": self.model.bucket_bytes,
                 "tbo_min": self.model.tbo_min, "graph_keys": sorted(self.graphs),
                 "decode_schedule": sorted(self.decode_schedule.items()), "rsag_mode": self.model.rsag_mode,
@@ -594,6 +607,11 @@ class LLMEngine:
                 raise ValueError("logit_bias, banned_token_ids, allowed_token_ids or min_tokens was requested but the "
                                  "engine was launched without them (LLMEngine(constraints=True), server --constraints)")
             edits = resolve_token_edits(params, self.eos, self.cfg.vocab_size)  # range, capacity, empty set
+        if params.has_min_p:
+            params.validate()
+            if not self.min_p:
+                raise ValueError("min_p was requested but the engine was launched without it "
+                                 "(LLMEngine(min_p=True), server --min-p)")
         prompt = list(int(t) for t in prompt_ids)
         if not prompt:
             raise ValueError("empty prompt")
@@ -742,6 +760,12 @@ class LLMEngine:
         seeds = step_seeds(np.array([r.seed for r in reqs], dtype=np.uint64),
                            np.array([len(r.output_ids) for r in reqs], dtype=np.int64))
         return temp, topk, topp, seeds
+
+    def _lnmp_array(self, reqs: List[Request]):
+        """The rows' ln(min_p) for the sampler (-inf: no floor), or None on an engine without min_p."""
+        if not self.min_p:
+            return None
+        return np.array([r.params.k_ln_min_p for r in reqs], dtype=np.float32)
 
     def step(self) -> List[StepEvent]:
         """One engine iteration; returns the token events it completed.
@@ -904,9 +928,11 @@ class LLMEngine:
             self.model.hidden_states(inp, self.kv)  # prompt chunks only: fill the cache, nothing to sample
             return []
         temp, topk, topp, seeds = self._sampling_arrays(reqs)
+        lnmp = self._lnmp_array(reqs)
         tok = self._forward_sample(inp, *(torch.from_numpy(a).to(dev) for a in (temp, topk, topp, seeds)),
                                    dist=self._dist_ok(temp, topk), pen=self._pen_eager(reqs),
-                                   con=self._con_eager(reqs))
+                                   con=self._con_eager(reqs),
+                                   lnmp=None if lnmp is None else torch.from_numpy(lnmp).to(dev))
         self._step_lps = self._lps_to_host()
         return tok.cpu().tolist()
 
@@ -929,13 +955,14 @@ class LLMEngine:
         return ops.apply_token_edits(logits, self.edit_ids, self.edit_vals, self.edit_meta, slots, nout, lo, vocab, out)
 
     def _forward_sample(self, inp: StepInput, temp, topk, topp, seeds, out=None, dist=False, lp_out=None, pen=None,
-                        con=None):
+                        con=None, lnmp=None):
         """Forward + LM head + sampler. ``dist``: each rank keeps its logit shard and only candidates
         are gathered (ops.sample_distributed); otherwise the [B, V] logits are all-gathered. With max_logprobs > 0
         a separate launch after the sampler reads the same logits and the sampled ids (ops.token_logprobs; on the
         ``dist`` path per-shard packs, an all-gather and a combine) into ``lp_out`` or ``self._lps``. ``pen``: the
         sampler reads the penalised copy of the logits (_penalise); ``con``: then the constrained copy of those
-        (_constrain); the log-probabilities stay those of the raw ones."""
+        (_constrain); the log-probabilities stay those of the raw ones. ``lnmp``: the rows' ln(min_p) - the sampler
+        applies the min-p floor, relative to the maximum of the row it reads (the penalised and constrained one)."""
         m = self.model
         V = self.cfg.vocab_size
         N = self.max_logprobs
@@ -947,7 +974,8 @@ class LLMEngine:
             plocal = local if pen is None else self._penalise(local, pen, m.vocab_lo, V)
             if con is not None:
                 plocal = self._constrain(plocal, con, m.vocab_lo, V)
-            tok = ops.sample_distributed(plocal, self.tp, m.vocab_lo, V, temp, topk, topp, seeds, out=out)
+            tok = ops.sample_distributed(plocal, self.tp, m.vocab_lo, V, temp, topk, topp, seeds, out=out,
+                                         ln_min_p=lnmp)
             if N > 0:
                 self._lps = ops.token_logprobs_distributed(local, self.tp, m.vocab_lo, V, tok, N, out=lp_out)
             return tok
@@ -957,9 +985,9 @@ class LLMEngine:
         if con is not None:
             plogits = self._constrain(plogits, con, 0, vocab)
         if logits.is_cuda:
-            tok = _hip_ops.sample(plogits, temp, topk, topp, seeds, vocab=vocab, out=out)
+            tok = _hip_ops.sample(plogits, temp, topk, topp, seeds, vocab=vocab, out=out, ln_min_p=lnmp)
         else:
-            tok = ops.sample(plogits, temp, topk, topp, seeds, vocab=vocab)
+            tok = ops.sample(plogits, temp, topk, topp, seeds, vocab=vocab, ln_min_p=lnmp)
         if N > 0:
             self._lps = ops.token_logprobs(logits, vocab, tok, N, out=lp_out)
         return tok
@@ -980,7 +1008,8 @@ class LLMEngine:
             if self.penalties else None
         con = (buf.cslot[:b], buf.cnout[:b], buf) if self.constraints else None
         self._forward_sample(inp, buf.temp[:b], buf.topk[:b], buf.topp[:b], buf.seeds[:b], out=buf.out[:b],
-                             dist=dist, lp_out=buf.lp_out(b), pen=pen, con=con)
+                             dist=dist, lp_out=buf.lp_out(b), pen=pen, con=con,
+                             lnmp=buf.lnmp[:b] if self.min_p else None)
 
     def _decode_cpu(self, batch, reqs: List[Request]) -> List[int]:
         ids = np.array([r.last_id for r in reqs], dtype=np.int64)
@@ -991,7 +1020,7 @@ class LLMEngine:
                         ctx_lens=torch.from_numpy(batch.ctx_lens.astype(np.int32)), max_ctx=self.max_model_len,
                         window=self.window)
         tok = self._forward_sample(inp, temp, topk, topp, seeds, dist=self._dist_ok(temp, topk),
-                                   pen=self._pen_eager(reqs), con=self._con_eager(reqs))
+                                   pen=self._pen_eager(reqs), con=self._con_eager(reqs), lnmp=self._lnmp_array(reqs))
         self._step_lps = self._lps_to_host()
         return tok.tolist()
 
@@ -1007,7 +1036,7 @@ class LLMEngine:
         if last is not None and last["ids"].shape == ids.shape and np.array_equal(last["ids"], ids) \
                 and last["keep"].all() and not (fresh is not None and fresh.any()) and not took:
             c = {k: last[k] for k in ("temp", "topk", "topp", "seed", "maxnew") + (("pen",) if self.penalties else ())
-                 + (("con",) if self.constraints else ())}
+                 + (("con",) if self.constraints else ()) + (("lnmp",) if self.min_p else ())}
             c["nout"] = last["nout"] + 1
             c["last"] = last["tokens"]
         else:
@@ -1024,6 +1053,8 @@ class LLMEngine:
                     c["pnew"] = np.where(fresh, -1, c["last"])
             if self.constraints:
                 c["con"] = self._con_slots(reqs)
+            if self.min_p:
+                c["lnmp"] = self._lnmp_array(reqs)
         c.update(ids=ids, reqs=reqs, n=len(reqs), pos=batch.positions, ctx=batch.ctx_lens.astype(np.int32),
                  slots=batch.slots, bt=batch.block_table, keep=np.ones(len(reqs), dtype=bool))
         c["dist"] = self._dist_ok(c["temp"], c["topk"])
@@ -1040,7 +1071,7 @@ class LLMEngine:
             buf.fill(k, b, None if device_ids else rec.pop("last"), rec["pos"], rec["slots"],
                      step_seeds(rec["seed"], rec["nout"]), rec["ctx"], rec["topk"], rec["bt"], rec["temp"],
                      rec["topp"], pen=rec.get("pen"),
-                     con=(rec["con"], rec["nout"]) if self.constraints else None)
+                     con=(rec["con"], rec["nout"]) if self.constraints else None, lnmp=rec.get("lnmp"))
             key = (b, bool(rec["dist"]))
             if self._host_prof:
                 # was the GPU already idle (every earlier step done) when this step was launched?
@@ -1093,7 +1124,8 @@ class LLMEngine:
             self._note_live_blocks()
             self.stats["spec_block_reserves"] = self.stats.get("spec_block_reserves", 0) + int(cross.size)
         dead = ~alive
-        rec = {k: cur[k] for k in ("ids", "reqs", "n", "temp", "topk", "topp", "seed", "maxnew", "dist")}
+        rec = {k: cur[k] for k in ("ids", "reqs", "n", "temp", "topk", "topp", "seed", "maxnew", "dist")
+               + (("lnmp",) if self.min_p else ())}  # a dead row is sampled greedily (top_k 1): its floor is unread
         rec["bt"] = bt
         rec["pos"] = nxt_pos
         rec["ctx"] = np.where(alive, cur["ctx"] + 1, 0).astype(np.int32)
@@ -1169,6 +1201,8 @@ class LLMEngine:
             buf.pslot.fill_(-1)  # padded rows hold no penalty slot: the launch copies them
         if self.constraints:
             buf.cslot.fill_(-1)  # nor a constraint slot
+        if self.min_p:
+            buf.lnmp.fill_(float("-inf"))  # nor a floor
         modes = self._decode_modes()
         # warm-up passes (lazy allocations, first launches). Native RCCL: with real collectives, so each
         # algorithm's lazy peer connection happens here and not inside the capture. torch's RCCL process

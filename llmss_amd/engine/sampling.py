@@ -69,6 +69,15 @@ class SamplingParams:
     banned_token_ids: List[int] = field(default_factory=list)
     allowed_token_ids: List[int] = field(default_factory=list)
     min_tokens: int = 0
+    # min-p: after temperature, top-k and top-p, keep only the tokens whose probability is at least min_p times the most
+    # likely token's (csrc/sampling.hip MINP variants; ops/reference.py _select is the definition). 0 = off; 1 keeps
+    # exactly the most likely token(s). Greedy requests ignore it. Anything but 0 needs an engine launched with
+    # min_p=True.
+    min_p: float = 0.0
+
+    @property
+    def has_min_p(self) -> bool:
+        return not (_is_number(self.min_p) and self.min_p == 0.0)
 
     @property
     def has_penalties(self) -> bool:
@@ -111,6 +120,8 @@ class SamplingParams:
                 raise ValueError("Values of logit_bias should be finite numbers in [-100, 100].")
         if not (_is_int(self.min_tokens) and 0 <= self.min_tokens <= self.max_new_tokens):
             raise ValueError("Value of min_tokens should be an integer in 0..max_new_tokens.")
+        if not (_is_number(self.min_p) and math.isfinite(self.min_p) and 0.0 <= self.min_p <= 1.0):
+            raise ValueError("Value of min_p should be a finite number in [0, 1].")
         return self
 
     def resolved_seed(self) -> int:
@@ -130,6 +141,14 @@ class SamplingParams:
     @property
     def k_top_p(self) -> float:
         return float(self.top_p)
+
+    @property
+    def k_ln_min_p(self) -> float:
+        """fp32 ln(min_p), computed in fp64 and rounded once; -inf (no floor) for min_p == 0 or a greedy request. The
+        kernels add it to the row's maximum scaled logit and never take a logarithm themselves."""
+        if self.is_greedy or not self.min_p > 0.0:
+            return float("-inf")
+        return float(np.float32(math.log(float(self.min_p))))
 
 
 def resolve_token_edits(params: SamplingParams, eos: Optional[int], vocab: int

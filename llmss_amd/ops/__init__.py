@@ -99,11 +99,13 @@ def linear(x, w, bias=None, act="none", glu=False, w_scale: Optional[torch.Tenso
     return ref.linear(x, w, bias, act, glu, w_scale)
 
 
-def sample(logits, temperature, top_k, top_p, seeds, vocab=None):
+def sample(logits, temperature, top_k, top_p, seeds, vocab=None, ln_min_p=None):
+    """``ln_min_p`` [B] fp32 (None: off): the min-p floor, ln(min_p) per row and -inf where a row has none
+    (ops/reference.py _select is the definition)."""
     if logits.is_cuda:
-        return _hip().sample(logits, temperature, top_k, top_p, seeds, vocab)
+        return _hip().sample(logits, temperature, top_k, top_p, seeds, vocab, ln_min_p=ln_min_p)
     lg = logits if vocab is None else logits[:, :vocab]
-    return ref.sample(lg, temperature, top_k, top_p, seeds)
+    return ref.sample(lg, temperature, top_k, top_p, seeds, ln_min_p=ln_min_p)
 
 
 def cross_entropy(logits, labels, ignore_index: int = -100):
@@ -140,18 +142,20 @@ def cand_ok(temperature, top_k) -> bool:
     return bool(np.all(~(t > 0) | (k == 1) | ((k >= 1) & (k <= CAND_K))))
 
 
-def sample_distributed(local, tp, lo, V, temperature, top_k, top_p, seeds, out=None, shards=1):
+def sample_distributed(local, tp, lo, V, temperature, top_k, top_p, seeds, out=None, shards=1, ln_min_p=None):
     """Vocab-parallel sampling without gathering logits: per-rank candidates -> all-gather -> select.
     ``local`` = this rank's [B, V/tp] logit shard whose first column is global token ``lo``; ``shards`` > 1
-    additionally cuts it into column shards inside one launch (a single GPU's full vocabulary)."""
+    additionally cuts it into column shards inside one launch (a single GPU's full vocabulary). ``ln_min_p``: as
+    for sample; the floor is relative to the maximum over the candidates, which is the row's."""
     if local.is_cuda:
         h = _hip()
         pack = h.cand_topk(local, lo, V, temperature, top_k, shards=shards)
         allp = tp.all_gather_last_dim(pack)
-        return h.sample_cand(allp, h.CAND_KC, temperature, top_k, top_p, seeds, out=out)
+        return h.sample_cand(allp, h.CAND_KC, temperature, top_k, top_p, seeds, out=out, ln_min_p=ln_min_p)
     pack = ref.cand_topk(local, lo, V, temperature, top_k, CAND_K, CAND_KC)
     allp = tp.all_gather_last_dim(pack)
-    y = ref.sample_cand(allp, allp.shape[1] // (2 * CAND_KC), CAND_KC, temperature, top_k, top_p, seeds, V)
+    y = ref.sample_cand(allp, allp.shape[1] // (2 * CAND_KC), CAND_KC, temperature, top_k, top_p, seeds, V,
+                        ln_min_p=ln_min_p)
     return _into(y, out)
 
 

@@ -803,8 +803,19 @@ def cand_topk(local, lo, V, temperature, top_k, K=CAND_K, KC=CAND_KC, out=None, 
     return pack
 
 
-def sample_cand(pack, KC, temperature, top_k, top_p, seeds, out=None, out2=None):
-    """Sample from gathered candidates ``pack`` [B, groups * 2*KC] (rank-major)."""
+def _ln_min_p_arg(ln_min_p, B, device):
+    """Checked ``ln_min_p`` [B] fp32 (ln of each row's min_p, -inf = off) -> pointer extras of the launch; none
+    without it, which runs the kernels without the min-p floor."""
+    if ln_min_p is None:
+        return ()
+    _check(ln_min_p.dtype == torch.float32 and ln_min_p.dim() == 1 and ln_min_p.numel() >= B
+           and ln_min_p.is_contiguous() and ln_min_p.is_cuda and ln_min_p.device == device,
+           "ln_min_p must be torch.float32 [B] on the logits' device")
+    return (ln_min_p.data_ptr(),)
+
+
+def sample_cand(pack, KC, temperature, top_k, top_p, seeds, out=None, out2=None, ln_min_p=None):
+    """Sample from gathered candidates ``pack`` [B, groups * 2*KC] (rank-major). ``ln_min_p``: see sample."""
     _check(pack.is_cuda and pack.dtype == torch.float32 and pack.dim() == 2 and pack.stride(1) == 1, "pack")
     B = pack.shape[0]
     _check(pack.shape[1] % (2 * KC) == 0, "pack width must be a multiple of 2*KC")
@@ -812,13 +823,18 @@ def sample_cand(pack, KC, temperature, top_k, top_p, seeds, out=None, out2=None)
     for t, dt, nm in ((temperature, torch.float32, "temperature"), (top_k, torch.int32, "top_k"),
                       (top_p, torch.float32, "top_p"), (seeds, torch.int64, "seeds")):
         _check(t.dtype == dt and t.numel() >= B and t.is_contiguous() and t.is_cuda, f"{nm} must be {dt}")
+    extra = _ln_min_p_arg(ln_min_p, B, pack.device)
     y = out if out is not None else torch.empty(B, dtype=torch.int64, device=pack.device)
     lib().sample_cand(pack.data_ptr(), pack.stride(0), B, groups, int(KC), temperature.data_ptr(), top_k.data_ptr(),
-                      top_p.data_ptr(), seeds.data_ptr(), y.data_ptr(), _ptr(out2), _stream())
+                      top_p.data_ptr(), seeds.data_ptr(), y.data_ptr(), _ptr(out2), _stream(), *extra)
     return y
 
 
-def sample(logits, temperature, top_k, top_p, seeds, vocab: Optional[int] = None, out=None, out2=None):
+def sample(logits, temperature, top_k, top_p, seeds, vocab: Optional[int] = None, out=None, out2=None,
+           ln_min_p=None):
+    """``ln_min_p`` [B] fp32 (None: off): the min-p floor as fp32 ln(min_p) per row, -inf where a row has none.
+    A non-greedy row keeps, after top-k and top-p, only tokens with scaled logit >= max + ln_min_p (the MINP
+    kernel variants of csrc/sampling.hip; ops/reference.py _select is the definition)."""
     _check(logits.is_cuda and logits.dim() == 2 and logits.stride(1) == 1, "logits [B, V]")
     _check(logits.dtype in (torch.bfloat16, torch.float32), "logits bf16/fp32")
     B = logits.shape[0]
@@ -828,9 +844,10 @@ def sample(logits, temperature, top_k, top_p, seeds, vocab: Optional[int] = None
                       (top_p, torch.float32, "top_p"), (seeds, torch.int64, "seeds")):
         if t is not None:
             _check(t.dtype == dt and t.numel() >= B and t.is_contiguous() and t.is_cuda, f"{nm} must be {dt}")
+    extra = _ln_min_p_arg(ln_min_p, B, logits.device)
     y = out if out is not None else torch.empty(B, dtype=torch.int64, device=logits.device)
     lib().sample(logits.data_ptr(), logits.stride(0), logits.dtype == torch.float32, B, V, _ptr(temperature),
-                 _ptr(top_k), _ptr(top_p), _ptr(seeds), y.data_ptr(), _ptr(out2), _stream())
+                 _ptr(top_k), _ptr(top_p), _ptr(seeds), y.data_ptr(), _ptr(out2), _stream(), *extra)
     return y
 
 

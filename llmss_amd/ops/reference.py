@@ -399,8 +399,13 @@ def _gumbel_u(r: np.ndarray) -> np.ndarray:
     return np.minimum(u, np.nextafter(np.float32(1), np.float32(0)))
 
 
-def _select(x: np.ndarray, idx: np.ndarray, t: float, k: int, p: float, seed: int, V: int) -> int:
-    """One row: x = scaled logits of the (candidate) elements, idx their global token ids."""
+def _select(x: np.ndarray, idx: np.ndarray, t: float, k: int, p: float, seed: int, V: int,
+            ln_min_p: Optional[float] = None) -> int:
+    """One row: x = scaled logits of the (candidate) elements, idx their global token ids. ``ln_min_p`` (min-p):
+    fp32 ln(min_p), -inf or None = off. After top-k and top-p - the nucleus is computed WITHOUT the floor - a
+    non-greedy row also drops every token with x < fp32(mx + ln_min_p), mx = the row's maximum scaled logit: the
+    tokens whose probability is below min_p times the most likely token's. ``>=`` as floats: a token on the floor
+    stays, and the maxima always do."""
     valid = np.isfinite(x) | (x > -np.inf)
     x, idx = x[valid], idx[valid]
     if x.size == 0:
@@ -422,6 +427,8 @@ def _select(x: np.ndarray, idx: np.ndarray, t: float, k: int, p: float, seed: in
             j = int(np.searchsorted(cum, np.uint64(target), side="left"))
             tp = kept[min(j, kept.size - 1)]
             thr = max(thr, tp)
+        if ln_min_p is not None:
+            thr = max(thr, np.float32(mx + np.float32(ln_min_p)))  # one fp32 add; -inf changes nothing
     v = x.astype(np.float32)
     if not greedy:
         keep = x >= thr
@@ -433,8 +440,9 @@ def _select(x: np.ndarray, idx: np.ndarray, t: float, k: int, p: float, seed: in
     return int(idx[v == best].min())
 
 
-def sample(logits: torch.Tensor, temperature, top_k, top_p, seeds, generator=None) -> torch.Tensor:
-    """Full-row sampler (the GPU ``sample_v3`` definition): temperature -> top-k -> top-p -> Gumbel-max."""
+def sample(logits: torch.Tensor, temperature, top_k, top_p, seeds, generator=None, ln_min_p=None) -> torch.Tensor:
+    """Full-row sampler (the GPU ``sample_v3`` definition): temperature -> top-k -> top-p -> min-p -> Gumbel-max.
+    ``ln_min_p`` [B] fp32 (None = off): see _select."""
     B, V = logits.shape
     lg = logits.detach().float().cpu().numpy()
     out = torch.empty(B, dtype=torch.long)
@@ -445,7 +453,7 @@ def sample(logits: torch.Tensor, temperature, top_k, top_p, seeds, generator=Non
         sc = np.float32(1.0) if (not t > 0 or k == 1) else np.float32(1.0) / np.float32(t)
         x = lg[b].astype(np.float32) * sc
         seed = int(seeds[b]) & ((1 << 64) - 1) if seeds is not None else 0
-        out[b] = _select(x, np.arange(V), t, k, p, seed, V)
+        out[b] = _select(x, np.arange(V), t, k, p, seed, V, None if ln_min_p is None else float(ln_min_p[b]))
     return out.to(logits.device)
 
 
@@ -474,8 +482,10 @@ def cand_topk(local: torch.Tensor, lo: int, V: int, temperature, top_k, K: int, 
     return torch.from_numpy(pack).to(local.device)
 
 
-def sample_cand(pack: torch.Tensor, groups: int, KC: int, temperature, top_k, top_p, seeds, V: int) -> torch.Tensor:
-    """Sampling over gathered candidates [B, groups * 2KC] (GPU ``sample_cand``)."""
+def sample_cand(pack: torch.Tensor, groups: int, KC: int, temperature, top_k, top_p, seeds, V: int,
+                ln_min_p=None) -> torch.Tensor:
+    """Sampling over gathered candidates [B, groups * 2KC] (GPU ``sample_cand``). The min-p floor is relative to the
+    maximum over the candidates, which is the row's: every shard contributes its largest elements."""
     B = pack.shape[0]
     a = pack.detach().cpu().numpy().reshape(B, groups, 2, KC)
     out = torch.empty(B, dtype=torch.long)
@@ -486,7 +496,7 @@ def sample_cand(pack: torch.Tensor, groups: int, KC: int, temperature, top_k, to
         k = int(top_k[b]) if top_k is not None else 0
         p = float(top_p[b]) if top_p is not None else 1.0
         seed = int(seeds[b]) & ((1 << 64) - 1) if seeds is not None else 0
-        out[b] = _select(x, idx, t, k, p, seed, V)
+        out[b] = _select(x, idx, t, k, p, seed, V, None if ln_min_p is None else float(ln_min_p[b]))
     return out.to(pack.device)
 
 

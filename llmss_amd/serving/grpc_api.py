@@ -53,7 +53,8 @@ def _build_pool():
                             ("prompt_token_ids", I32, 1), ("ignore_eos", B, 0), ("return_logprobs", B, 0),
                             ("top_logprobs", I32, 0), ("repetition_penalty", FL, 0), ("presence_penalty", FL, 0),
                             ("frequency_penalty", FL, 0), ("logit_bias_ids", I32, 1), ("logit_bias_values", FL, 1),
-                            ("banned_token_ids", I32, 1), ("allowed_token_ids", I32, 1), ("min_tokens", I32, 0)])
+                            ("banned_token_ids", I32, 1), ("allowed_token_ids", I32, 1), ("min_tokens", I32, 0),
+                            ("min_p", FL, 0)])
     msg("TopLogprobs", [("token_ids", I32, 1), ("logprobs", FL, 1)])
     msg("GenerateResponse", [("prompt", S, 0), ("continuation", S, 0), ("request_id", S, 0), ("token_ids", I32, 1),
                              ("finish_reason", S, 0), ("ttft_s", FL, 0), ("e2e_s", FL, 0), ("token_logprobs", FL, 1),
@@ -117,10 +118,10 @@ def _constraint_fields(req) -> dict:
 
 
 def _params(req, max_logprobs: Optional[int] = None, penalties: Optional[bool] = None,
-            constraints: Optional[bool] = None):
+            constraints: Optional[bool] = None, min_p: Optional[bool] = None):
     """``max_logprobs``: the serving engine's launch-time limit when known - a log-probability request it cannot
     serve is a ValueError here (INVALID_ARGUMENT), not a failed handle later. ``penalties``, ``constraints``: likewise
-    whether the engine was launched with penalties / token constraints."""
+    whether the engine was launched with penalties / token constraints / min-p."""
     from ..engine.sampling import SamplingParams
 
     logprobs = int(req.top_logprobs) if req.return_logprobs else None
@@ -137,12 +138,14 @@ def _params(req, max_logprobs: Optional[int] = None, penalties: Optional[bool] =
     if constraints is False and (con["logit_bias"] or con["banned_token_ids"] or con["allowed_token_ids"]
                                  or con["min_tokens"]):
         raise ValueError("token constraints are not enabled on this server (--constraints)")
+    if min_p is False and float(req.min_p) != 0.0:  # proto3: 0 (unset) is off
+        raise ValueError("min_p is not enabled on this server (--min-p)")
     # proto3 scalars default to 0: 0 means "reference default" for max_new_tokens/temperature/top_p
     # (0 is invalid for them) and "disabled" for top_k (as in the reference CLI, generate.py:30).
     return SamplingParams(max_new_tokens=req.max_new_tokens or 20, is_greedy=req.is_greedy,
                           temperature=req.temperature or 1.0, top_p=req.top_p or 0.95, top_k=req.top_k,
                           seed=req.seed or None, ignore_eos=req.ignore_eos, logprobs=logprobs, **pen,
-                          **con).validate()
+                          **con, min_p=float(req.min_p)).validate()
 
 
 def add_servicer(server: grpc.Server, servicer) -> None:
@@ -331,6 +334,9 @@ class EngineServicer:
     def _constraints(self):
         return getattr(getattr(self.driver, "engine", None), "constraints", None)
 
+    def _min_p(self):
+        return getattr(getattr(self.driver, "engine", None), "min_p", None)
+
     def _prompt_ids(self, req):
         from ..utils.tokenizer import encode
 
@@ -340,7 +346,7 @@ class EngineServicer:
 
     async def Generate(self, req, ctx):
         try:
-            params = _params(req, self._max_logprobs(), self._penalties(), self._constraints())
+            params = _params(req, self._max_logprobs(), self._penalties(), self._constraints(), self._min_p())
         except ValueError as e:
             await ctx.abort(grpc.StatusCode.INVALID_ARGUMENT, str(e))
         loop = asyncio.get_running_loop()
@@ -369,7 +375,7 @@ class EngineServicer:
 
     async def GenerateStream(self, req, ctx):
         try:
-            params = _params(req, self._max_logprobs(), self._penalties(), self._constraints())
+            params = _params(req, self._max_logprobs(), self._penalties(), self._constraints(), self._min_p())
         except ValueError as e:
             await ctx.abort(grpc.StatusCode.INVALID_ARGUMENT, str(e))
         loop = asyncio.get_running_loop()
@@ -429,7 +435,7 @@ class BrokerServicer:
                        temperature=req.temperature or 1.0, top_p=req.top_p or 0.95, top_k=req.top_k or 50,
                        request_id=rid, seed=req.seed or None, ignore_eos=req.ignore_eos, stream=stream,
                        logprobs=int(req.top_logprobs) if req.return_logprobs else None, **_penalty_fields(req),
-                       **_constraint_fields(req),
+                       **_constraint_fields(req), min_p=float(req.min_p),
                        prompt_token_ids=list(req.prompt_token_ids) or None, deadline_s=deadline_s)
 
     def Generate(self, req, ctx):

@@ -29,6 +29,9 @@ def add_engine_args(p):
                    help="serve logit_bias / banned_token_ids / allowed_token_ids / min_tokens: keeps every running "
                         "sequence's resolved token lists on the device (max_num_seqs x 8 KiB); off: requests that "
                         "set one are rejected")
+    g.add_argument("--min-p", "--min_p", dest="min_p", action="store_true",
+                   help="serve min_p: stages one more float per row and samples through the min-p variants of the "
+                        "sampler kernels; off: requests that set it are rejected")
     g.add_argument("--dp", type=int, default=1,
                    help="data-parallel replicas: with torchrun, world = dp x tp (each replica's leader serves "
                         "from the broker); in a single process, one TP=1 replica per GPU behind a Router")
@@ -43,7 +46,8 @@ def _engine(model_path, tp, dev, args, tok=None):
                     block_size=args.block_size, max_model_len=args.max_model_len, use_graphs=not args.no_graphs,
                     eos_token_id=getattr(tok, "eos_token_id", None), max_logprobs=getattr(args, "max_logprobs", 0),
                     penalties=bool(getattr(args, "penalties", False)),
-                    constraints=bool(getattr(args, "constraints", False)))
+                    constraints=bool(getattr(args, "constraints", False)),
+                    min_p=bool(getattr(args, "min_p", False)))
     return eng, tok, model
 
 

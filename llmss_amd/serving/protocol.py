@@ -44,6 +44,8 @@ class Request(BaseModel):
     banned_token_ids: List[int] = Field(default_factory=list)
     allowed_token_ids: List[int] = Field(default_factory=list)
     min_tokens: int = 0
+    # min-p in [0, 1], 0 = off (SamplingParams; the serving engine needs --min-p, else the reply is an error)
+    min_p: float = 0.0
 
 
 class Response(BaseModel):
@@ -77,7 +79,8 @@ def to_sampling(req: Request) -> SamplingParams:
                           logprobs=req.logprobs, repetition_penalty=req.repetition_penalty,
                           presence_penalty=req.presence_penalty, frequency_penalty=req.frequency_penalty,
                           logit_bias=dict(req.logit_bias), banned_token_ids=list(req.banned_token_ids),
-                          allowed_token_ids=list(req.allowed_token_ids), min_tokens=req.min_tokens).validate()
+                          allowed_token_ids=list(req.allowed_token_ids), min_tokens=req.min_tokens,
+                          min_p=req.min_p).validate()
 
 
 def dump_response(resp: Dict[str, Any]) -> str:
