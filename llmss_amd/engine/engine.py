@@ -24,7 +24,7 @@ import math
 import os
 import time
 from dataclasses import dataclass, field
-from typing import Dict, Iterable, List, Optional, Sequence, Tuple
+from typing import Dict, Iterable, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -36,8 +36,14 @@ from ..utils.logging import get_logger
 from ..utils.tracing import PhaseTimer
 from ..utils.tracing import range as trace_range
 from .sampling import MAX_TOKEN_EDITS, MAX_TOP_LOGPROBS, SamplingParams, resolve_token_edits, step_seeds
+from .staging import LANES, SLOT_LANES, SlotPool, _DecodeBuffers
 
 log = get_logger(__name__)
+
+# optional staging lane (staging.LANES) -> the SamplingParams field it stages; the slot lanes come from the engine's
+# pools and cnout from the step's nout
+_LANE_PARAM = {"rep": "repetition_penalty", "pres": "presence_penalty", "freq": "frequency_penalty",
+               "lnmp": "k_ln_min_p"}
 
 # context length (cached positions per row) at which the capture-time A/Bs time their candidates - the GQA decode
 # attention kernels and the decode schedules: the bench's mean over a 128-token prompt + 128 generated tokens
@@ -89,130 +95,16 @@ class StepEvent:
     top_logprobs: Optional[List[Tuple[int, float]]] = None
 
 
-class _DecodeBuffers:
-    """Static device buffers feeding the captured decode graphs, filled by ONE host-to-device copy
-    per step from one of two pinned staging sets: with decode steps pipelined (LLMEngine.step),
-    the host fills step t+1's set while step t's copy may still be queued, so a set is rewritten
-    only after the step that used it has been collected. Token ids come back through two pinned
-    output buffers for the same reason. ``max_logprobs`` N > 0 adds the log-probability outputs: ``lp_f`` [max_b, 1 + N]
-    fp32 (the sampled token's, then the top N) and ``lp_i`` [max_b, N] int32 (their ids) with two pinned host sets.
-    ``penalties`` appends ``pslot`` (i32, after the block tables) and ``rep`` / ``pres`` / ``freq`` (f32, after top_p) to
-    the staging blob - without it every offset is as before - and keeps the penalised logits, one static buffer per
-    logits width (``pen_out``). ``constraints`` appends ``cslot`` and ``cnout`` (i32, after ``pslot`` when both are on)
-    and keeps the constrained logits the same way (``con_out``). ``min_p`` appends ``lnmp`` (f32, the rows' ln(min_p),
-    at the end of the f32 section: after ``freq`` when penalties are on)."""
-
-    def __init__(self, max_b: int, max_blocks: int, device, max_logprobs: int = 0, penalties: bool = False,
-                 constraints: bool = False, min_p: bool = False):
-        B, MB = max_b, max_blocks
-        self.max_b, self.max_blocks = B, MB
-        self.penalties = bool(penalties)
-        self.constraints = bool(constraints)
-        self.min_p = bool(min_p)
-        pin = torch.cuda.is_available() and device.type == "cuda"
-        # ids|pos|slots|seeds (i64) | ctx|topk|bt[|pslot][|cslot|cnout] (i32) | temp|topp[|rep|pres|freq][|lnmp] (f32)
-        self.o32 = 4 * B * 8
-        self.of32 = self.o32 + (2 * B + B * MB + (B if penalties else 0) + (2 * B if constraints else 0)) * 4
-        self.o_lnmp = (5 if penalties else 2) * B  # f32 words before lnmp
-        nbytes = self.of32 + (self.o_lnmp + (B if min_p else 0)) * 4
-        self.h = [torch.zeros(nbytes, dtype=torch.uint8, pin_memory=pin) for _ in range(2)]
-        self.d = torch.zeros(nbytes, dtype=torch.uint8, device=device)
-        self.d_i64 = self.d[:self.o32].view(torch.int64)
-        self.d_i32 = self.d[self.o32:self.of32].view(torch.int32)
-        self.d_f32 = self.d[self.of32:].view(torch.float32)
-        self.out = torch.zeros(max_b, dtype=torch.int64, device=device)
-        self.h_out = [torch.zeros(max_b, dtype=torch.int64, pin_memory=pin) for _ in range(2)]
-        self.ids, self.pos, self.slots, self.seeds = (self.d_i64[i * B:(i + 1) * B] for i in range(4))
-        self.ctx, self.topk = self.d_i32[:B], self.d_i32[B:2 * B]
-        self.bt = self.d_i32[2 * B:2 * B + B * MB].view(B, max_blocks)
-        self.temp, self.topp = self.d_f32[:B], self.d_f32[B:2 * B]
-        if penalties:
-            self.pslot = self.d_i32[2 * B + B * MB:3 * B + B * MB]
-            self.rep, self.pres, self.freq = (self.d_f32[i * B:(i + 1) * B] for i in (2, 3, 4))
-            self._pen_out = {}
-        if constraints:
-            self.o_con = 2 * B + B * MB + (B if penalties else 0)  # int32 words before cslot
-            self.cslot = self.d_i32[self.o_con:self.o_con + B]
-            self.cnout = self.d_i32[self.o_con + B:self.o_con + 2 * B]
-            self._con_out = {}
-        self.lnmp = self.d_f32[self.o_lnmp:self.o_lnmp + B] if min_p else None
-        N = self.max_logprobs = max_logprobs
-        if N > 0:
-            self.lp_f = torch.zeros(max_b, 1 + N, dtype=torch.float32, device=device)
-            self.lp_i = torch.zeros(max_b, N, dtype=torch.int32, device=device)
-            self.h_lp_f = [torch.zeros(max_b, 1 + N, dtype=torch.float32, pin_memory=pin) for _ in range(2)]
-            self.h_lp_i = [torch.zeros(max_b, N, dtype=torch.int32, pin_memory=pin) for _ in range(2)]
-
-    def lp_out(self, b: int):
-        """The kernels' (lp, top_lp, top_ids) outputs for the first b rows, or None without log-probabilities."""
-        if self.max_logprobs <= 0:
-            return None
-        return self.lp_f[:b, 0], self.lp_f[:b, 1:], self.lp_i[:b]
-
-    def pen_out(self, b: int, like: torch.Tensor) -> torch.Tensor:
-        """The static buffer the penalised copy of the [b, width] logits ``like`` goes to. Made at the first (warm-up)
-        call for a width and kept for the buffers' lifetime: captured graphs write and read it."""
-        key = (like.shape[1], like.dtype)
-        if key not in self._pen_out:
-            self._pen_out[key] = torch.zeros(self.max_b, like.shape[1], dtype=like.dtype, device=like.device)
-        return self._pen_out[key][:b]
-
-    def con_out(self, b: int, like: torch.Tensor) -> torch.Tensor:
-        """The static buffer the constrained copy of the [b, width] logits ``like`` goes to (as ``pen_out``, and
-        apart from it: the penalised logits are the constraint launch's input)."""
-        key = (like.shape[1], like.dtype)
-        if key not in self._con_out:
-            self._con_out[key] = torch.zeros(self.max_b, like.shape[1], dtype=like.dtype, device=like.device)
-        return self._con_out[key][:b]
-
-    def fill(self, k, b_pad, ids, pos, slots, seeds, ctx, topk, bt, temp, topp, pen=None, con=None, lnmp=None):
-        """Stage one step's inputs in set k and copy them to the device. ``ids=None``: the input ids
-        are the previous step's sampled tokens, copied on the device (same rows). ``pen``: the rows' (penalty slot,
-        repetition, presence, frequency) arrays; padded rows get slot -1. ``con``: the rows' (constraint slot, tokens
-        generated so far) arrays; padded rows get slot -1. ``lnmp``: the rows' ln(min_p); padded rows (and every row
-        without it) get -inf, no floor."""
-        n = len(pos)
-        B, MB = self.max_b, self.max_blocks
-        h = self.h[k]
-        hi = h[:self.o32].view(torch.int64).numpy()
-        hi32 = h[self.o32:self.of32].view(torch.int32).numpy()
-        hf = h[self.of32:].view(torch.float32).numpy()
-        for j, arr in enumerate((ids, pos, slots, seeds)):
-            if arr is not None:
-                hi[j * B:j * B + n] = arr
-            hi[j * B + n:j * B + b_pad] = -1 if j == 2 else 0  # padded rows: no cache write
-        hi32[:n] = ctx
-        hi32[n:b_pad] = 0
-        hi32[B:B + n] = topk
-        hi32[B + n:B + b_pad] = 1
-        btv = hi32[2 * B:2 * B + B * MB].reshape(B, MB)
-        btv[:n, :bt.shape[1]] = bt
-        btv[n:b_pad] = 0
-        hf[:n] = temp
-        hf[n:b_pad] = 0
-        hf[B:B + n] = topp
-        hf[B + n:B + b_pad] = 1
-        if self.penalties:
-            ps = hi32[2 * B + B * MB:3 * B + B * MB]
-            ps[:b_pad] = -1
-            if pen is not None:
-                ps[:n] = pen[0]
-                for j, arr in enumerate(pen[1:], start=2):
-                    hf[j * B:j * B + n] = arr
-        if self.constraints:
-            cs = hi32[self.o_con:self.o_con + 2 * B]
-            cs[:b_pad] = -1
-            cs[B:B + b_pad] = 0
-            if con is not None:
-                cs[:n] = con[0]
-                cs[B:B + n] = con[1]
-        if self.min_p:
-            hf[self.o_lnmp:self.o_lnmp + b_pad] = -np.inf
-            if lnmp is not None:
-                hf[self.o_lnmp:self.o_lnmp + n] = lnmp
-        self.d.copy_(h, non_blocking=True)
-        if ids is None:
-            self.ids[:n].copy_(self.out[:n])
+class _SamplerIn(NamedTuple):
+    """A sampling step's per-row inputs on the step's device: built from the requests for an eager step
+    (LLMEngine._sample_eager), views of the decode buffers for a graph step (LLMEngine._decode_forward)."""
+    temp: torch.Tensor
+    topk: torch.Tensor
+    topp: torch.Tensor
+    seeds: torch.Tensor
+    lnmp: Optional[torch.Tensor] = None  # ln(min_p), -inf: no floor; None on an engine without min_p
+    pen: Optional[tuple] = None  # (state row, token to register, repetition, presence, frequency); None: no launch
+    con: Optional[tuple] = None  # (constraint slot, tokens generated so far); None: no launch
 
 
 class LLMEngine:
@@ -242,6 +134,8 @@ class LLMEngine:
         if not (isinstance(max_logprobs, int) and 0 <= max_logprobs <= MAX_TOP_LOGPROBS):
             raise ValueError(f"max_logprobs must be an integer in 0..{MAX_TOP_LOGPROBS}, not {max_logprobs!r}")
         self.max_logprobs = max_logprobs
+        # the optional lanes a decode step's record carries, by this engine's options
+        self._lane_names = tuple(l.name for l in LANES if l.when and getattr(self, l.when) and l.name != "cnout")
         self._step_lps = None  # (values [n, 1 + N], ids [n, N]) of the last eager sampling step, on the host
         if kv_dtype is not None:  # "bf16" (model dtype) or "fp8" (e4m3 rows + per-row scale)
             if kv_dtype not in ("bf16", "fp8"):
@@ -262,20 +156,19 @@ class LLMEngine:
         # take the minimum
         # penalty state before the KV cache is sized, so that _auto_blocks sees the memory it takes
         self.pen_state = None
-        self._pen_free: List[int] = list(range(max_num_seqs - 1, -1, -1))  # free state rows (pop() takes the lowest)
-        self._pen_slot: Dict[int, int] = {}  # request id -> state row; holders are always running sequences
+        self._pen_pool = SlotPool(max_num_seqs)  # the state rows
+        self._pen_free, self._pen_slot = self._pen_pool.free, self._pen_pool.held
+        for opt in ("penalties", "constraints"):
+            if getattr(self, opt) and model.dtype not in (torch.bfloat16, torch.float32):
+                raise ValueError(f"{opt} need bfloat16 or float32 logits, the model computes {model.dtype}")
         if self.penalties:
-            if model.dtype not in (torch.bfloat16, torch.float32):
-                raise ValueError(f"penalties need bfloat16 or float32 logits, the model computes {model.dtype}")
             self.pen_state = torch.zeros(max_num_seqs, self.cfg.vocab_size, dtype=torch.int32, device=self.device)
         # constraint state, likewise: one block per slot - early and late ids, early and late values, meta - so that
         # one host-to-device copy writes a slot whole; edit_ids / edit_vals / edit_meta are views of it
         self.con_state = None
-        self._con_free: List[int] = list(range(max_num_seqs - 1, -1, -1))
-        self._con_slot: Dict[int, int] = {}  # request id -> constraint slot; holders are always running sequences
+        self._con_pool = SlotPool(max_num_seqs)
+        self._con_free, self._con_slot = self._con_pool.free, self._con_pool.held
         if self.constraints:
-            if model.dtype not in (torch.bfloat16, torch.float32):
-                raise ValueError(f"constraints need bfloat16 or float32 logits, the model computes {model.dtype}")
             E = MAX_TOKEN_EDITS
             self.con_state = torch.zeros(max_num_seqs, 4 * E + 4, dtype=torch.int32, device=self.device)
             self.edit_ids = self.con_state[:, :2 * E].view(max_num_seqs, 2, E)
@@ -587,31 +480,28 @@ class LLMEngine:
     def add_request(self, prompt_ids: Sequence[int], params: Optional[SamplingParams] = None,
                     req_id: Optional[int] = None) -> int:
         params = params or SamplingParams()
-        if params.logprobs is not None:
-            params.validate()
-            if self.max_logprobs == 0:
-                raise ValueError("log-probabilities were requested but the engine was launched without them "
-                                 "(LLMEngine(max_logprobs=N), server --max-logprobs N)")
-            if params.logprobs > self.max_logprobs:
-                raise ValueError(f"logprobs = {params.logprobs} exceeds the engine's max_logprobs = "
-                                 f"{self.max_logprobs}")
-        if params.has_penalties:
-            params.validate()
-            if not self.penalties:
-                raise ValueError("a repetition, presence or frequency penalty was requested but the engine was "
-                                 "launched without them (LLMEngine(penalties=True), server --penalties)")
+
+        def gate(wanted, enabled, message) -> bool:  # an option the request asks for: valid, and the engine has it
+            if wanted:
+                params.validate()
+                if not enabled:
+                    raise ValueError(message)
+            return wanted
+
+        if gate(params.logprobs is not None, self.max_logprobs > 0,
+                "log-probabilities were requested but the engine was launched without them "
+                "(LLMEngine(max_logprobs=N), server --max-logprobs N)") and params.logprobs > self.max_logprobs:
+            raise ValueError(f"logprobs = {params.logprobs} exceeds the engine's max_logprobs = {self.max_logprobs}")
+        gate(params.has_penalties, self.penalties,
+             "a repetition, presence or frequency penalty was requested but the engine was "
+             "launched without them (LLMEngine(penalties=True), server --penalties)")
         edits = None
-        if params.has_constraints:
-            params.validate()
-            if not self.constraints:
-                raise ValueError("logit_bias, banned_token_ids, allowed_token_ids or min_tokens was requested but the "
-                                 "engine was launched without them (LLMEngine(constraints=True), server --constraints)")
+        if gate(params.has_constraints, self.constraints,
+                "logit_bias, banned_token_ids, allowed_token_ids or min_tokens was requested but the "
+                "engine was launched without them (LLMEngine(constraints=True), server --constraints)"):
             edits = resolve_token_edits(params, self.eos, self.cfg.vocab_size)  # range, capacity, empty set
-        if params.has_min_p:
-            params.validate()
-            if not self.min_p:
-                raise ValueError("min_p was requested but the engine was launched without it "
-                                 "(LLMEngine(min_p=True), server --min-p)")
+        gate(params.has_min_p, self.min_p,
+             "min_p was requested but the engine was launched without it (LLMEngine(min_p=True), server --min-p)")
         prompt = list(int(t) for t in prompt_ids)
         if not prompt:
             raise ValueError("empty prompt")
@@ -634,8 +524,7 @@ class LLMEngine:
             self.sched.abort(rid)
             r = self.requests[rid]
             r.finished, r.finish_reason = True, "abort"
-            self._pen_release(rid)
-            self._con_release(rid)
+            self._release_slots(rid)
             if self._pending:  # rows of in-flight decode steps: no speculative successor may touch it
                 self._aborted.add(rid)
 
@@ -649,20 +538,13 @@ class LLMEngine:
             self._aborted.discard(r.id)
         return done
 
-    # -------------------------------------------------------------------------- penalties
-    def _pen_release(self, rid: int):
-        """Give a request's state row back (finish, abort, preemption). A decode step still in flight may go on
-        registering tokens into the row: the next holder's penalty_reset rebuilds it whole, later on the same stream."""
-        s = self._pen_slot.pop(rid, None)
-        if s is not None:
-            self._pen_free.append(s)
-
-    def _pen_arrays(self, reqs: List[Request]):
-        """(slot, repetition, presence, frequency) rows of a step; slot -1 where the request holds no state row."""
-        return (np.array([self._pen_slot.get(r.id, -1) for r in reqs], dtype=np.int32),
-                np.array([r.params.repetition_penalty for r in reqs], dtype=np.float32),
-                np.array([r.params.presence_penalty for r in reqs], dtype=np.float32),
-                np.array([r.params.frequency_penalty for r in reqs], dtype=np.float32))
+    # -------------------------------------------------------------------------- penalty rows, constraint slots
+    def _release_slots(self, rid: int):
+        """Give a request's penalty state row and its constraint slot back (finish, abort, preemption). A decode step
+        still in flight may go on registering tokens into the row and reading the slot: the next holder's
+        penalty_reset rebuilds the row whole, and its copy overwrites the slot, later on the same stream."""
+        self._pen_pool.release(rid)
+        self._con_pool.release(rid)
 
     def _pen_acquire(self, reqs: List[Request]) -> np.ndarray:
         """Give every request of a sampling step that asks for penalties and holds no state row one, rebuilt in one
@@ -676,9 +558,8 @@ class LLMEngine:
             if r.id in self._pen_slot or not r.params.has_penalties:
                 continue
             fresh[i] = True
-            self._pen_slot[r.id] = self._pen_free.pop()
+            rs.append(self._pen_pool.take(r.id))
             t, w = ops.penalty_words(r.prompt_ids, r.output_ids)
-            rs.append(self._pen_slot[r.id])
             toks.append(t)
             words.append(w)
             cu.append(cu[-1] + t.size)
@@ -689,26 +570,6 @@ class LLMEngine:
                               torch.from_numpy(np.concatenate(toks)).to(dev),
                               torch.from_numpy(np.concatenate(words)).to(dev))
         return fresh
-
-    def _pen_eager(self, reqs: List[Request]):
-        """Penalty inputs of an eager sampling step over ``reqs`` (_forward_sample's ``pen``), or None when no row
-        holds a state row (the launch would be a copy)."""
-        if not self.penalties:
-            return None
-        fresh = self._pen_acquire(reqs)
-        slot, rep, pres, freq = self._pen_arrays(reqs)
-        if not (slot >= 0).any():
-            return None
-        new = np.where(fresh, -1, np.array([r.last_id for r in reqs], dtype=np.int64))
-        return tuple(torch.from_numpy(a).to(self.device) for a in (slot, new, rep, pres, freq)) + (None,)
-
-    # -------------------------------------------------------------------------- token constraints
-    def _con_release(self, rid: int):
-        """Give a request's constraint slot back (finish, abort, preemption). A decode step still in flight may go on
-        reading it: the next holder's copy overwrites it later on the same stream."""
-        s = self._con_slot.pop(rid, None)
-        if s is not None:
-            self._con_free.append(s)
 
     def _con_acquire(self, reqs: List[Request]) -> bool:
         """Give every request of a sampling step that has constraints and holds no slot the lowest free one, its
@@ -722,8 +583,7 @@ class LLMEngine:
         for r in reqs:
             if r.edits is None or r.id in self._con_slot:
                 continue
-            self._con_free.sort(reverse=True)
-            s = self._con_slot[r.id] = self._con_free.pop()
+            s = self._con_pool.take(r.id)
             early, late, fill = r.edits
             ids, vals, meta = ops.pack_token_edits(early, late, fill, r.params.min_tokens, E)
             rows[s] = np.concatenate([ids.reshape(-1), vals.reshape(-1).view(np.int32), meta])
@@ -737,36 +597,52 @@ class LLMEngine:
             i = j
         return bool(rows)
 
-    def _con_slots(self, reqs: List[Request]) -> np.ndarray:
-        return np.array([self._con_slot.get(r.id, -1) for r in reqs], dtype=np.int32)
+    # -------------------------------------------------------------------------- sampler inputs
+    def _sampling_arrays(self, reqs: List[Request]) -> dict:
+        """The requests' sampler constants and position: a step's Philox keys are step_seeds(seed, nout)."""
+        return {"temp": np.array([r.params.k_temperature for r in reqs], dtype=np.float32),
+                "topk": np.array([r.params.k_top_k for r in reqs], dtype=np.int32),
+                "topp": np.array([r.params.k_top_p for r in reqs], dtype=np.float32),
+                "seed": np.array([r.seed for r in reqs], dtype=np.uint64),
+                "nout": np.array([len(r.output_ids) for r in reqs], dtype=np.int64)}
 
-    def _con_eager(self, reqs: List[Request]):
-        """Constraint inputs of an eager sampling step over ``reqs`` (_forward_sample's ``con``), or None when no row
-        holds a slot (the launch would be a copy)."""
-        if not self.constraints:
-            return None
-        self._con_acquire(reqs)
-        slot = self._con_slots(reqs)
-        if not (slot >= 0).any():
-            return None
-        nout = np.array([len(r.output_ids) for r in reqs], dtype=np.int32)
-        return torch.from_numpy(slot).to(self.device), torch.from_numpy(nout).to(self.device), None
+    def _lane(self, name: str, reqs: List[Request]) -> np.ndarray:
+        """One optional staging lane (staging.LANES) of a step's rows: the requests' slots of a pool (-1: holds none),
+        or their SamplingParams field (fp32 lanes all)."""
+        if name in SLOT_LANES:
+            pool = self._pen_pool if name == "pslot" else self._con_pool
+            return np.array([pool.get(r.id) for r in reqs], dtype=np.int32)
+        return np.array([getattr(r.params, _LANE_PARAM[name]) for r in reqs], dtype=np.float32)
+
+    def _sample_eager(self, inp: StepInput, reqs: List[Request]) -> List[int]:
+        """Forward and sample an eager step for ``reqs``, its sampler inputs built here; requests that hold no state
+        row or constraint slot yet take one. ``pen`` / ``con`` stay None when no row holds one (the launch would be a
+        copy). Returns the tokens and leaves the step's log-probabilities in ``_step_lps``."""
+        def d(a):
+            return torch.from_numpy(a).to(self.device)
+
+        a = self._sampling_arrays(reqs)
+        temp, topk, topp, seeds = (d(x) for x in (a["temp"], a["topk"], a["topp"], step_seeds(a["seed"], a["nout"])))
+        pen = con = lnmp = None
+        if self.penalties:
+            fresh = self._pen_acquire(reqs)
+            pslot = self._lane("pslot", reqs)
+            if (pslot >= 0).any():
+                new = np.where(fresh, -1, np.array([r.last_id for r in reqs], dtype=np.int64))
+                pen = tuple(d(x) for x in (pslot, new, *(self._lane(name, reqs) for name in ("rep", "pres", "freq"))))
+        if self.constraints:
+            self._con_acquire(reqs)
+            cslot = self._lane("cslot", reqs)
+            if (cslot >= 0).any():
+                con = d(cslot), d(a["nout"].astype(np.int32))
+        if self.min_p:
+            lnmp = d(self._lane("lnmp", reqs))
+        tok = self._forward_sample(inp, _SamplerIn(temp, topk, topp, seeds, lnmp, pen, con),
+                                   dist=self._dist_ok(a["temp"], a["topk"]))
+        self._step_lps = self._lps_to_host()
+        return tok.cpu().tolist()
 
     # -------------------------------------------------------------------------- step
-    def _sampling_arrays(self, reqs: List[Request]):
-        temp = np.array([r.params.k_temperature for r in reqs], dtype=np.float32)
-        topk = np.array([r.params.k_top_k for r in reqs], dtype=np.int32)
-        topp = np.array([r.params.k_top_p for r in reqs], dtype=np.float32)
-        seeds = step_seeds(np.array([r.seed for r in reqs], dtype=np.uint64),
-                           np.array([len(r.output_ids) for r in reqs], dtype=np.int64))
-        return temp, topk, topp, seeds
-
-    def _lnmp_array(self, reqs: List[Request]):
-        """The rows' ln(min_p) for the sampler (-inf: no floor), or None on an engine without min_p."""
-        if not self.min_p:
-            return None
-        return np.array([r.params.k_ln_min_p for r in reqs], dtype=np.float32)
-
     def step(self) -> List[StepEvent]:
         """One engine iteration; returns the token events it completed.
 
@@ -805,8 +681,7 @@ class LLMEngine:
             raise RuntimeError(f"scheduler returned an idle step with {self.sched.num_waiting()} waiting and "
                                f"{self.sched.num_running()} running sequences")
         for rid in batch.preempted.tolist():  # recomputed later: the re-prefill takes a state row again
-            self._pen_release(int(rid))
-            self._con_release(int(rid))
+            self._release_slots(int(rid))
         if batch.kind != 0:
             self.stats["preemptions"] += len(batch.preempted)
             ids = batch.ids
@@ -874,8 +749,7 @@ class LLMEngine:
             else:
                 continue
             fins[i] = True
-            self._pen_release(r.id)
-            self._con_release(r.id)
+            self._release_slots(r.id)
         self.sched.on_tokens(ids, fins)
         self._last_fins = fins
         self.stats["steps"] += 1
@@ -927,53 +801,48 @@ class LLMEngine:
         if not reqs:
             self.model.hidden_states(inp, self.kv)  # prompt chunks only: fill the cache, nothing to sample
             return []
-        temp, topk, topp, seeds = self._sampling_arrays(reqs)
-        lnmp = self._lnmp_array(reqs)
-        tok = self._forward_sample(inp, *(torch.from_numpy(a).to(dev) for a in (temp, topk, topp, seeds)),
-                                   dist=self._dist_ok(temp, topk), pen=self._pen_eager(reqs),
-                                   con=self._con_eager(reqs),
-                                   lnmp=None if lnmp is None else torch.from_numpy(lnmp).to(dev))
-        self._step_lps = self._lps_to_host()
-        return tok.cpu().tolist()
+        return self._sample_eager(inp, reqs)
 
     def _dist_ok(self, temp, topk) -> bool:
         """Sample this step from vocab-parallel candidates (no [B, V] logits all-gather)?"""
         return self.dist_sampling and ops.cand_ok(temp, topk)
 
-    def _penalise(self, logits, pen, lo, vocab):
-        """The penalty launch between the LM head and the sampler: ``pen`` = (slots, new tokens, repetition, presence,
-        frequency, static decode buffers or None). Out of place - the raw logits stay for the log-probabilities."""
-        slots, new, rep, pres, freq, buf = pen
-        out = buf.pen_out(logits.shape[0], logits) if buf is not None else None
-        return ops.apply_penalties(logits, self.pen_state, slots, new, rep, pres, freq, lo, vocab, out)
+    def _edit_logits(self, logits, smp: _SamplerIn, lo, vocab, buf):
+        """The penalty launch (``smp.pen``), then the constraint launch (``smp.con``), between the LM head and the
+        sampler. Out of place - the raw logits stay for the log-probabilities - and into ``buf``'s static buffers when
+        the step is fed from the decode buffers."""
+        b = logits.shape[0]
+        if smp.pen is not None:
+            out = buf.logits_out("pen", b, logits) if buf is not None else None
+            logits = ops.apply_penalties(logits, self.pen_state, *smp.pen, lo, vocab, out)
+        if smp.con is not None:
+            out = buf.logits_out("con", b, logits) if buf is not None else None
+            logits = ops.apply_token_edits(logits, self.edit_ids, self.edit_vals, self.edit_meta, *smp.con, lo, vocab,
+                                           out)
+        return logits
 
-    def _constrain(self, logits, con, lo, vocab):
-        """The constraint launch between the penalties and the sampler: ``con`` = (slots, tokens generated so far,
-        static decode buffers or None). Out of place - the raw logits stay for the log-probabilities."""
-        slots, nout, buf = con
-        out = buf.con_out(logits.shape[0], logits) if buf is not None else None
-        return ops.apply_token_edits(logits, self.edit_ids, self.edit_vals, self.edit_meta, slots, nout, lo, vocab, out)
-
-    def _forward_sample(self, inp: StepInput, temp, topk, topp, seeds, out=None, dist=False, lp_out=None, pen=None,
-                        con=None, lnmp=None):
+    def _forward_sample(self, inp: StepInput, smp: _SamplerIn, dist=False, buf: Optional[_DecodeBuffers] = None):
         """Forward + LM head + sampler. ``dist``: each rank keeps its logit shard and only candidates
         are gathered (ops.sample_distributed); otherwise the [B, V] logits are all-gathered. With max_logprobs > 0
         a separate launch after the sampler reads the same logits and the sampled ids (ops.token_logprobs; on the
-        ``dist`` path per-shard packs, an all-gather and a combine) into ``lp_out`` or ``self._lps``. ``pen``: the
-        sampler reads the penalised copy of the logits (_penalise); ``con``: then the constrained copy of those
-        (_constrain); the log-probabilities stay those of the raw ones. ``lnmp``: the rows' ln(min_p) - the sampler
-        applies the min-p floor, relative to the maximum of the row it reads (the penalised and constrained one)."""
+        ``dist`` path per-shard packs, an all-gather and a combine) into ``self._lps``. ``smp.pen``: the sampler reads
+        the penalised copy of the logits; ``smp.con``: then the constrained copy of those (_edit_logits); the
+        log-probabilities stay those of the raw ones. ``smp.lnmp``: the rows' ln(min_p) - the sampler applies the
+        min-p floor, relative to the maximum of the row it reads (the penalised and constrained one).
+        ``buf``: ``smp`` is views of these decode buffers, and tokens, log-probabilities and the edited logits go to
+        their static outputs."""
         m = self.model
         V = self.cfg.vocab_size
         N = self.max_logprobs
+        temp, topk, topp, seeds, lnmp = smp[:5]
+        b = temp.shape[0]
+        out, lp_out = (buf.out[:b], buf.lp_out(b)) if buf is not None else (None, None)
         if dist:
             h = m.hidden_states(inp, self.kv)
             if inp.last_idx is not None:
                 h = h.index_select(0, inp.last_idx)
             local = m.local_logits(h)
-            plocal = local if pen is None else self._penalise(local, pen, m.vocab_lo, V)
-            if con is not None:
-                plocal = self._constrain(plocal, con, m.vocab_lo, V)
+            plocal = self._edit_logits(local, smp, m.vocab_lo, V, buf)
             tok = ops.sample_distributed(plocal, self.tp, m.vocab_lo, V, temp, topk, topp, seeds, out=out,
                                          ln_min_p=lnmp)
             if N > 0:
@@ -981,9 +850,7 @@ class LLMEngine:
             return tok
         logits = m(inp, self.kv)
         vocab = min(V, logits.shape[-1])
-        plogits = logits if pen is None else self._penalise(logits, pen, 0, vocab)
-        if con is not None:
-            plogits = self._constrain(plogits, con, 0, vocab)
+        plogits = self._edit_logits(logits, smp, 0, vocab, buf)
         if logits.is_cuda:
             tok = _hip_ops.sample(plogits, temp, topk, topp, seeds, vocab=vocab, out=out, ln_min_p=lnmp)
         else:
@@ -1004,25 +871,21 @@ class LLMEngine:
                         block_tables=buf.bt[:b], ctx_lens=buf.ctx[:b], max_ctx=self.max_model_len,
                         decode_splits=self._splits(b), window=self.window)
         # every decode step registers its input token before the penalties are applied
-        pen = (buf.pslot[:b], buf.ids[:b] if pnew is None else pnew, buf.rep[:b], buf.pres[:b], buf.freq[:b], buf) \
+        pen = (buf.pslot[:b], buf.ids[:b] if pnew is None else pnew, buf.rep[:b], buf.pres[:b], buf.freq[:b]) \
             if self.penalties else None
-        con = (buf.cslot[:b], buf.cnout[:b], buf) if self.constraints else None
-        self._forward_sample(inp, buf.temp[:b], buf.topk[:b], buf.topp[:b], buf.seeds[:b], out=buf.out[:b],
-                             dist=dist, lp_out=buf.lp_out(b), pen=pen, con=con,
-                             lnmp=buf.lnmp[:b] if self.min_p else None)
+        con = (buf.cslot[:b], buf.cnout[:b]) if self.constraints else None
+        smp = _SamplerIn(buf.temp[:b], buf.topk[:b], buf.topp[:b], buf.seeds[:b],
+                         buf.lnmp[:b] if self.min_p else None, pen, con)
+        self._forward_sample(inp, smp, dist=dist, buf=buf)
 
     def _decode_cpu(self, batch, reqs: List[Request]) -> List[int]:
         ids = np.array([r.last_id for r in reqs], dtype=np.int64)
-        temp, topk, topp, seeds = self._sampling_arrays(reqs)
         inp = StepInput(kind="decode", input_ids=torch.from_numpy(ids), positions=torch.from_numpy(batch.positions),
                         slots=torch.from_numpy(batch.slots),
                         block_tables=torch.from_numpy(batch.block_table.astype(np.int32)),
                         ctx_lens=torch.from_numpy(batch.ctx_lens.astype(np.int32)), max_ctx=self.max_model_len,
                         window=self.window)
-        tok = self._forward_sample(inp, temp, topk, topp, seeds, dist=self._dist_ok(temp, topk),
-                                   pen=self._pen_eager(reqs), con=self._con_eager(reqs), lnmp=self._lnmp_array(reqs))
-        self._step_lps = self._lps_to_host()
-        return tok.tolist()
+        return self._sample_eager(inp, reqs)
 
     # ------------------------------------------------------------------ pipelined GPU decode
     def _record_from_batch(self, batch, ids: np.ndarray, reqs: List[Request]) -> dict:
@@ -1035,26 +898,17 @@ class LLMEngine:
         took = self._con_acquire(reqs) if self.constraints else False
         if last is not None and last["ids"].shape == ids.shape and np.array_equal(last["ids"], ids) \
                 and last["keep"].all() and not (fresh is not None and fresh.any()) and not took:
-            c = {k: last[k] for k in ("temp", "topk", "topp", "seed", "maxnew") + (("pen",) if self.penalties else ())
-                 + (("con",) if self.constraints else ()) + (("lnmp",) if self.min_p else ())}
+            c = {k: last[k] for k in ("temp", "topk", "topp", "seed", "maxnew", "lanes")}
             c["nout"] = last["nout"] + 1
             c["last"] = last["tokens"]
         else:
-            c = {"temp": np.array([r.params.k_temperature for r in reqs], dtype=np.float32),
-                 "topk": np.array([r.params.k_top_k for r in reqs], dtype=np.int32),
-                 "topp": np.array([r.params.k_top_p for r in reqs], dtype=np.float32),
-                 "seed": np.array([r.seed for r in reqs], dtype=np.uint64),
-                 "maxnew": np.array([r.params.max_new_tokens for r in reqs], dtype=np.int64),
-                 "nout": np.array([len(r.output_ids) for r in reqs], dtype=np.int64),
-                 "last": np.array([r.last_id for r in reqs], dtype=np.int64)}
-            if self.penalties:
-                c["pen"] = self._pen_arrays(reqs)
-                if fresh.any():  # rows whose reset covers their input token: this step registers nothing for them
-                    c["pnew"] = np.where(fresh, -1, c["last"])
-            if self.constraints:
-                c["con"] = self._con_slots(reqs)
-            if self.min_p:
-                c["lnmp"] = self._lnmp_array(reqs)
+            c = self._sampling_arrays(reqs)
+            c.update(maxnew=np.array([r.params.max_new_tokens for r in reqs], dtype=np.int64),
+                     last=np.array([r.last_id for r in reqs], dtype=np.int64),
+                     lanes={name: self._lane(name, reqs) for name in self._lane_names})
+            if fresh is not None and fresh.any():
+                # rows whose reset covers their input token: this step registers nothing for them
+                c["pnew"] = np.where(fresh, -1, c["last"])
         c.update(ids=ids, reqs=reqs, n=len(reqs), pos=batch.positions, ctx=batch.ctx_lens.astype(np.int32),
                  slots=batch.slots, bt=batch.block_table, keep=np.ones(len(reqs), dtype=bool))
         c["dist"] = self._dist_ok(c["temp"], c["topk"])
@@ -1067,11 +921,13 @@ class LLMEngine:
         k = self._stage
         self._stage ^= 1
         buf = self.buf
+        lanes = rec["lanes"]
+        if self.constraints:
+            lanes = dict(lanes, cnout=rec["nout"])
         with self.timer.phase("decode"):
             buf.fill(k, b, None if device_ids else rec.pop("last"), rec["pos"], rec["slots"],
                      step_seeds(rec["seed"], rec["nout"]), rec["ctx"], rec["topk"], rec["bt"], rec["temp"],
-                     rec["topp"], pen=rec.get("pen"),
-                     con=(rec["con"], rec["nout"]) if self.constraints else None, lnmp=rec.get("lnmp"))
+                     rec["topp"], **lanes)
             key = (b, bool(rec["dist"]))
             if self._host_prof:
                 # was the GPU already idle (every earlier step done) when this step was launched?
@@ -1124,20 +980,18 @@ class LLMEngine:
             self._note_live_blocks()
             self.stats["spec_block_reserves"] = self.stats.get("spec_block_reserves", 0) + int(cross.size)
         dead = ~alive
-        rec = {k: cur[k] for k in ("ids", "reqs", "n", "temp", "topk", "topp", "seed", "maxnew", "dist")
-               + (("lnmp",) if self.min_p else ())}  # a dead row is sampled greedily (top_k 1): its floor is unread
+        rec = {k: cur[k] for k in ("ids", "reqs", "n", "temp", "topk", "topp", "seed", "maxnew", "dist", "lanes")}
         rec["bt"] = bt
         rec["pos"] = nxt_pos
         rec["ctx"] = np.where(alive, cur["ctx"] + 1, 0).astype(np.int32)
         rec["slots"] = slots
         rec["nout"] = cur["nout"] + 1
         rec["keep"] = alive
-        if dead.any():
+        if dead.any():  # a dead row is sampled greedily (top_k 1): its penalties and its min-p floor are unread
             rec["topk"] = np.where(alive, cur["topk"], 1).astype(np.int32)
-        if self.penalties:  # dead rows hold no slot: their row of the state may already be another sequence's
-            rec["pen"] = (np.where(alive, cur["pen"][0], -1).astype(np.int32),) + tuple(cur["pen"][1:])
-        if self.constraints:  # likewise
-            rec["con"] = np.where(alive, cur["con"], -1).astype(np.int32)
+        if rec["lanes"]:  # dead rows hold no slot: their row of the state may already be another sequence's
+            rec["lanes"] = dict(cur["lanes"], **{name: np.where(alive, cur["lanes"][name], -1).astype(np.int32)
+                                                 for name in SLOT_LANES if name in cur["lanes"]})
         self._launch_decode(rec, device_ids=True)
 
     def _collect_decode(self):
@@ -1191,18 +1045,9 @@ class LLMEngine:
         """Capture one decode graph per batch bucket (largest first, shared memory pool)."""
         buf = self.buf
         pool = torch.cuda.graph_pool_handle()
-        # padded rows are harmless: ctx 0 -> zero attention, slot -1 -> no cache write
-        buf.d_i64.zero_()
-        buf.slots.fill_(-1)
-        buf.d_i32.zero_()
-        buf.topk.fill_(1)
-        buf.d_f32.zero_()
-        if self.penalties:
-            buf.pslot.fill_(-1)  # padded rows hold no penalty slot: the launch copies them
-        if self.constraints:
-            buf.cslot.fill_(-1)  # nor a constraint slot
-        if self.min_p:
-            buf.lnmp.fill_(float("-inf"))  # nor a floor
+        # every row padded: harmless (ctx 0 -> zero attention, slot -1 -> no cache write, no penalty or constraint
+        # slot -> the launches copy the row, no floor) and greedy
+        buf.reset()
         modes = self._decode_modes()
         # warm-up passes (lazy allocations, first launches). Native RCCL: with real collectives, so each
         # algorithm's lazy peer connection happens here and not inside the capture. torch's RCCL process

@@ -51,11 +51,7 @@ def test_warmup_covers_every_captured_collective(monkeypatch):
     m.col_mode = "auto"  # the A/B decides per bucket (forced mode would run it in every forward)
     e = LLMEngine(m, max_num_seqs=24, block_size=16, use_graphs=False, autotune=False, graph_buckets=[1, 8, 16, 24])
     buf = e.buf = _DecodeBuffers(e.buckets[-1], e.max_blocks, torch.device("cpu"))
-    buf.d_i64.zero_()
-    buf.slots.fill_(-1)
-    buf.d_i32.zero_()
-    buf.topk.fill_(1)
-    buf.d_f32.zero_()
+    buf.reset()
     modes = e._decode_modes()
     assert modes == (True, False)  # vocab-parallel: both samplers are captured
 

@@ -237,6 +237,46 @@ def test_opt_in_and_validation(ckpts):
     assert not on.has_unfinished() and not on.requests and idle(on)
 
 
+@pytest.mark.parametrize("how", ["finish", "abort", "preempt"])
+def test_both_slots_go_back_through_one_path(ckpts, plains, how):
+    """Requests that hold a penalty state row and a constraint slot give both back together, through
+    _release_slots and nowhere else, when they finish, are aborted or are preempted."""
+    d, _ = ckpts["llama"]
+    eng, cfg = _engine(d, constraints=True, penalties=True, **(dict(num_blocks=14) if how == "preempt" else {}))
+    both = derive(plains["llama"], cfg.vocab_size)[4]
+    assert both.has_penalties and both.has_constraints
+    inner, inside, released = eng._release_slots, [False], []
+
+    def counted(rid):
+        held = (rid in eng._pen_slot, rid in eng._con_slot)
+        inside[0] = True
+        inner(rid)
+        inside[0] = False
+        assert rid not in eng._pen_slot and rid not in eng._con_slot
+        released.append((rid, held))
+
+    def guarded(release):
+        def f(rid):
+            assert inside[0], "a pool released a slot outside _release_slots"
+            return release(rid)
+        return f
+    eng._release_slots = counted
+    eng._pen_pool.release, eng._con_pool.release = guarded(eng._pen_pool.release), guarded(eng._con_pool.release)
+    reqs = run(eng, PROMPTS, [SamplingParams(**both.__dict__) for _ in PROMPTS],
+               abort_after=(9, 1) if how == "abort" else None)
+    with_both = [rid for rid, held in released if held == (True, True)]
+    assert set(with_both) == {r.id for r in reqs}
+    assert all(held in ((True, True), (False, False)) for _, held in released)  # never one without the other
+    if how == "abort":
+        assert reqs[1].finish_reason == "abort" and 0 < len(reqs[1].output_ids) < NEW
+    if how == "preempt":  # a preempted request gives both back, takes them again at its re-prefill, and finishes
+        assert eng.stats["preemptions"] > 0 and len(reqs) < len(with_both) <= len(reqs) + eng.stats["preemptions"]
+    else:
+        assert len(with_both) == len(reqs)
+    assert all(len(r.output_ids) == NEW for r in reqs if r.finish_reason != "abort")
+    assert idle(eng)
+
+
 # ---------------------------------------------------------------------------------------- TP=2 over gloo
 def _free_port():
     s = socket.socket()

@@ -177,8 +177,8 @@ def test_default_requests_and_disabled_engine_unchanged(setup):
     assert off.constraints is False and off.con_state is None and "constraint_state_bytes" not in off.stats
     assert sorted(off.graphs) == sorted(on.graphs)
     buf, B, MB = off.buf, off.buf.max_b, off.buf.max_blocks
-    assert not hasattr(buf, "cslot") and not hasattr(buf, "cnout") and not hasattr(buf, "_con_out")
-    assert not hasattr(buf, "pslot") and not hasattr(buf, "rep") and not hasattr(buf, "_pen_out")
+    assert not hasattr(buf, "cslot") and not hasattr(buf, "cnout") and not hasattr(buf, "_logits_out")
+    assert not hasattr(buf, "pslot") and not hasattr(buf, "rep")
     assert buf.o32 == 32 * B and buf.of32 == buf.o32 + (2 * B + B * MB) * 4 and buf.d.numel() == buf.of32 + 8 * B
     assert buf.topp.data_ptr() + 4 * B == buf.d.data_ptr() + buf.d.numel()
     # on (penalties and constraints): pslot, then cslot and cnout, end the int32 part; rep / pres / freq the fp32 one
